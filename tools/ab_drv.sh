@@ -9,7 +9,7 @@ for rep in $(seq 1 $reps); do
     for cfg in 20:5 300:20; do
       k=${cfg%%:*}; w=${cfg#*:}
       out=$PWD/gpurun_out/ab/${name}_${k}_$rep.json
-      (cd $dir && timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-ttfs --steps $k --warmup $w > $out 2>/dev/null) || { echo "bench $name rc=$?"; exit 1; }
+      (cd $dir && timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-ttfs --steps $k --warmup $w > $out 2>/dev/null) || { echo "bench $name rc=$?"; exit 1; }
       python3 -c "import json;d=json.loads(open('$out').read().splitlines()[-1]);r=d['roofline'];print('$name K=$k',round(d['value']/1e9,3),round(d['ms_per_step']*1e3,2),r['avg_launch_us'])"
     done
   done

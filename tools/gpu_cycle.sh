@@ -48,7 +48,7 @@ ab)
             name=${spec%%=*}; dir=${spec#*=}
             for cfg in 20:5 300:20; do
                 k=${cfg%%:*}; w=${cfg#*:}; f="$R/$out/${name}_${k}_$rep.json"
-                (cd "$dir" && timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-ttfs --steps "$k" --warmup "$w" \
+                (cd "$dir" && timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-ttfs --steps "$k" --warmup "$w" \
                     > "$f" 2> "$f.err") || { echo "bench $name rc=$?"; tail -5 "$f.err"; exit 1; }
                 line "$f" "$name K=$k"
             done
@@ -61,7 +61,7 @@ abenv)
             name=${spec%%=*}; kv=${spec#*=}
             for cfg in 20:5 300:20; do
                 k=${cfg%%:*}; w=${cfg#*:}; f="$R/$out/${name}_${k}_$rep.json"
-                env "$kv" timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-ttfs --steps "$k" --warmup "$w" \
+                env "$kv" timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-ttfs --steps "$k" --warmup "$w" \
                     > "$f" 2> "$f.err" || { echo "bench $name rc=$?"; tail -5 "$f.err"; exit 1; }
                 line "$f" "$name K=$k"
             done
@@ -71,14 +71,14 @@ timeline)
     dir=$1; shift
     for it in "$@"; do
         (cd "$dir" && SBMP_TIMELINE_ITER=$it SBMP_TIMELINE_OUT="$R/$out/it$it.bin" timeout -k 10 120 python3 bench.py \
-            --no-cpu-baseline --no-ttfs --steps 30 --warmup 20 > "$R/$out/b$it.json" 2> "$R/$out/b$it.err") || exit 1
+            --full --no-cpu-baseline --no-ttfs --steps 30 --warmup 20 > "$R/$out/b$it.json" 2> "$R/$out/b$it.err") || exit 1
         python3 tools/timeline.py "$R/$out/it$it.bin" --step > "$R/$out/k_step_iter$it.txt" && head -30 "$R/$out/k_step_iter$it.txt"
     done ;;
 sq)
     cd /tmp && export TMPDIR=/tmp
     timeout -k 10 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES \
         SQ_BUSY_CYCLES SQ_WAIT_INST_ANY -d "$R/$out/sq" -o run --output-format csv -- python3 "$R/bench.py" \
-        --steps 30 --warmup 20 --no-cpu-baseline --no-ttfs "$@" > "$R/$out/sq.log" 2>&1 || exit 1
+        --full --steps 30 --warmup 20 --no-cpu-baseline --no-ttfs "$@" > "$R/$out/sq.log" 2>&1 || exit 1
     cd "$R" && python3 tools/pmc_summary.py "$out" --skip 25 > "$R/$out/sq_summary.txt" && sed -n 1,30p "$R/$out/sq_summary.txt" ;;
 pmc)
     bash tools/profile_pmc.sh "$out" "$@" || exit 1
@@ -86,16 +86,16 @@ pmc)
 trace)
     cd /tmp && export TMPDIR=/tmp
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/$out/trace" -o run --output-format csv -- \
-        python3 "$R/bench.py" "$@" > "$R/$out/bench.json" 2> "$R/$out/bench.err" || exit 1
+        python3 "$R/bench.py" --full "$@" > "$R/$out/bench.json" 2> "$R/$out/bench.err" || exit 1
     cd "$R" && line "$out/bench.json" traced ;;
 bench)
     name=$1; shift
-    timeout -k 10 300 python3 bench.py "$@" > "$R/$out/$name.json" 2> "$R/$out/$name.err" || { tail -5 "$R/$out/$name.err"; exit 1; }
+    timeout -k 10 300 python3 bench.py --full "$@" > "$R/$out/$name.json" 2> "$R/$out/$name.err" || { tail -5 "$R/$out/$name.err"; exit 1; }
     line "$R/$out/$name.json" "$name" ;;
 shard)
     timeout -k 10 300 python3 tools/shard_cost.py 1 2 8 > "$R/$out/shard_cost.txt" 2>&1 || exit 1
     cat "$R/$out/shard_cost.txt"
-    timeout -k 10 300 python3 bench.py --gpus 2 --collectives host --steps 50 --warmup 10 --no-cpu-baseline --no-ttfs \
+    timeout -k 10 300 python3 bench.py --full --gpus 2 --collectives host --steps 50 --warmup 10 --no-cpu-baseline --no-ttfs \
         > "$R/$out/bench_2rank_host.json" 2> "$R/$out/bench_2rank_host.err" || { tail -5 "$R/$out/bench_2rank_host.err"; exit 1; }
     tail -1 "$R/$out/bench_2rank_host.json" ;;
 final)
@@ -105,22 +105,22 @@ final)
     timeout -k 10 180 python3 -c "import __graft_entry__ as g; g.smoke()" > "$R/$out/smoke.log" 2>&1 \
         || { tail -5 "$R/$out/smoke.log"; exit 1; }
     tail -1 "$R/$out/smoke.log"
-    timeout -k 10 300 python3 bench.py > "$R/$out/bench.json" 2> "$R/$out/bench.err" || { tail -5 "$R/$out/bench.err"; exit 1; }
+    timeout -k 10 300 python3 bench.py --full > "$R/$out/bench.json" 2> "$R/$out/bench.err" || { tail -5 "$R/$out/bench.err"; exit 1; }
     line "$R/$out/bench.json" default
     for rep in 1 2; do
-        timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-ttfs > "$R/$out/drv_$rep.json" \
+        timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-ttfs > "$R/$out/drv_$rep.json" \
             2> "$R/$out/drv_$rep.err" || exit 1
         line "$R/$out/drv_$rep.json" "driver $rep"
     done
-    timeout -k 10 200 python3 bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-ttfs > "$R/$out/s300.json" \
+    timeout -k 10 200 python3 bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --no-ttfs > "$R/$out/s300.json" \
         2> "$R/$out/s300.err" || exit 1
     line "$R/$out/s300.json" s300
-    timeout -k 10 300 python3 bench.py --workload c5 --samples-per-gpu 131072 --warmup 5 --steps 35 --no-cpu-baseline --no-ttfs \
+    timeout -k 10 300 python3 bench.py --full --workload c5 --samples-per-gpu 131072 --warmup 5 --steps 35 --no-cpu-baseline --no-ttfs \
         > "$R/$out/c5_131k.json" 2> "$R/$out/c5_131k.err" || exit 1
     line "$R/$out/c5_131k.json" c5_131k
     cd /tmp && export TMPDIR=/tmp
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/$out/trace" -o run --output-format csv -- \
-        python3 "$R/bench.py" --no-cpu-baseline > "$R/$out/bench_traced.json" 2> "$R/$out/bench_traced.err" || exit 1
+        python3 "$R/bench.py" --full --no-cpu-baseline > "$R/$out/bench_traced.json" 2> "$R/$out/bench_traced.err" || exit 1
     cd "$R" && line "$out/bench_traced.json" traced ;;
 attrib)   # <workload> <samples> <iterations>: per-launch WRITE_SIZE / FETCH_SIZE fitted per unit of work
     wl=$1; ns=$2; it=$3; mkdir -p "$R/$out/$wl"; cd /tmp && export TMPDIR=/tmp

@@ -6,5 +6,5 @@ OUT=${1:-gpurun_out/pmc_sq}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 export TMPDIR=/tmp
 mkdir -p "$R/$OUT"
-ARGS="--steps 30 --warmup 20 --no-cpu-baseline --no-ttfs ${*:2}"
+ARGS="--full --steps 30 --warmup 20 --no-cpu-baseline --no-ttfs ${*:2}"
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY -d "$R/$OUT/sq" -o run --output-format csv -- python3 "$R/bench.py" $ARGS > "$R/$OUT/sq.log" 2>&1

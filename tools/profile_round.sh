@@ -9,6 +9,6 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p "$R/$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$R/$OUT/trace" -o run --output-format csv \
-    -- python3 "$R/bench.py" > "$R/$OUT/bench.json" 2> "$R/$OUT/bench.err"
+    -- python3 "$R/bench.py" --full > "$R/$OUT/bench.json" 2> "$R/$OUT/bench.err"
 cd "$R"
 tools/profile_pmc.sh "$OUT/pmc"

@@ -6,5 +6,5 @@ OUT=${1:-gpurun_out/trace}; shift || true
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 mkdir -p "$R/$OUT"
-ARGS="${*:---no-cpu-baseline --no-ttfs}"
+ARGS="--full ${*:---no-cpu-baseline --no-ttfs}"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/$OUT/trace" -o run --output-format csv -- python3 "$R/bench.py" $ARGS > "$R/$OUT/bench.json" 2> "$R/$OUT/bench.err"
