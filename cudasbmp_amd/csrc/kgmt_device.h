@@ -766,22 +766,6 @@ __device__ __forceinline__ bool grid_free_at(float minx, float miny, float maxx,
     else return grid_free_fast<kGridBatchGlobal>(minx, miny, maxx, maxy, d, G(d.gridStart));
 }
 
-// reference statePropagator.cu:5-76 (car).  Same operation sequence as the oracle
-// (D9-D11): fmaf where nvcc would contract, steering via one double fma.
-// v / agentLength: when agentLength is a power of two, v * (1/agentLength) is the
-// same correctly rounded value (both are the exact product scaled by 2^-k), so the
-// host passes invAgentLength != 0 and the per-step division disappears.
-// Exec-masked instead of the reference's per-lane break: a dead lane skips the
-// step body (the wave keeps iterating while any lane is alive); a lane that fails
-// the bounds test keeps its new (x, y) and its old (theta, v), a lane that fails the
-// collision test keeps the step's new (x, y, theta, v) -- exactly the state at the
-// reference's break (statePropagator.cu:42-45, 61-64).
-// Loop-invariant divisions by numDisc / agentLength use div_by when the host
-// verified the reciprocal (bit-exact; tools/check_fast_division.c).
-struct NoMidHook {
-    __device__ void operator()() const {}
-};
-
 // The controls of one child (statePropagator.cu:17-21): they depend on the slot's
 // XORWOW stream only, not on the parent, so k_step draws them while its block counts
 // are still in flight.  car: (a, steering, duration, dt, tan(steering));
@@ -810,12 +794,22 @@ __device__ __forceinline__ ChildCtl draw_controls(Xorwow& rs, const KgmtDev& d) 
     return c;
 }
 
-// midHook() runs once, before Euler step numDisc / 2, on every lane that entered (k_step
-// issues the planner-publication loads there: late enough to see them, early enough
-// that they have landed when propagation ends).
-template <int OBS, typename MidHook = NoMidHook, bool LDSG = false>
+// reference statePropagator.cu:5-76 (car).  Same operation sequence as the oracle
+// (D9-D11): fmaf where nvcc would contract, steering via one double fma.
+// v / agentLength: when agentLength is a power of two, v * (1/agentLength) is the
+// same correctly rounded value (both are the exact product scaled by 2^-k), so the
+// host passes invAgentLength != 0 and the per-step division disappears.
+// Exec-masked instead of the reference's per-lane break: a dead lane skips the
+// step body (the wave keeps iterating while any lane is alive); a lane that fails
+// the bounds test keeps its new (x, y) and its old (theta, v), a lane that fails the
+// collision test keeps the step's new (x, y, theta, v) -- exactly the state at the
+// reference's break (statePropagator.cu:42-45, 61-64).
+// Loop-invariant divisions by numDisc / agentLength use div_by when the host
+// verified the reciprocal (bit-exact; tools/check_fast_division.c).
+// LDSG: the grid index's cell-start table is read from LDS at sStart (k_step stages it).
+template <int OBS, bool LDSG = false>
 __device__ __forceinline__ bool car_euler(float4 p, const ChildCtl& ctl, const KgmtDev& d, const float4* obs,
-                                          ChildOut& out, MidHook midHook = MidHook(), const int* sStart = nullptr) {
+                                          ChildOut& out, const int* sStart = nullptr) {
     const float a = ctl.a, duration = ctl.dur, dt = ctl.dt, tan_steering = ctl.tanS;
     // (x, y) and (theta, v) as float pairs: each pair update is one v_pk_mul_f32 /
     // v_pk_fma_f32 doing the same IEEE operation per component (same bits).
@@ -866,15 +860,14 @@ __device__ __forceinline__ bool car_euler(float4 p, const ChildCtl& ctl, const K
         if (!oob) tv = ntv;
         alive = !oob & freeSeg;
     };
-    // two loops around the hook: no per-step test of the step index
+    // In two halves: as one loop of nSteps, k_expand's grid form comes out of the compiler
+    // with a private segment (tests/test_isa_hazards.py), and every form's code changes.
     const int nSteps = __builtin_amdgcn_readfirstlane(d.numDisc), midStep = nSteps >> 1;
     if (d.invAgentLength != 0.0f) {
         for (int i = 0; i < midStep; ++i) step(std::true_type());
-        midHook();
         for (int i = midStep; i < nSteps; ++i) step(std::true_type());
     } else {
         for (int i = 0; i < midStep; ++i) step(std::false_type());
-        midHook();
         for (int i = midStep; i < nSteps; ++i) step(std::false_type());
     }
     out.state = make_float4(xy.x, xy.y, tv.x, tv.y);
@@ -885,9 +878,9 @@ __device__ __forceinline__ bool car_euler(float4 p, const ChildCtl& ctl, const K
 }
 
 // Holonomic R2 point (build extension), predicated like car_euler.
-template <int OBS, typename MidHook = NoMidHook, bool LDSG = false>
+template <int OBS, bool LDSG = false>
 __device__ __forceinline__ bool point_euler(float4 p, const ChildCtl& ctl, const KgmtDev& d, const float4* obs,
-                                            ChildOut& out, MidHook midHook = MidHook(), const int* sStart = nullptr) {
+                                            ChildOut& out, const int* sStart = nullptr) {
     const float vx = ctl.a, vy = ctl.steer, duration = ctl.dur, dt = ctl.dt;
     float x = p.x, y = p.y;
     WaveCull cull{~0u, true};
@@ -912,10 +905,8 @@ __device__ __forceinline__ bool point_euler(float4 p, const ChildCtl& ctl, const
         y = ny;
         alive = !oob & freeSeg;
     };
-    const int nSteps = __builtin_amdgcn_readfirstlane(d.numDisc), midStep = nSteps >> 1;
-    for (int i = 0; i < midStep; ++i) step();
-    midHook();
-    for (int i = midStep; i < nSteps; ++i) step();
+    const int nSteps = __builtin_amdgcn_readfirstlane(d.numDisc);
+    for (int i = 0; i < nSteps; ++i) step();
     out.state = make_float4(x, y, 0.0f, 0.0f);
     out.a = vx;
     out.steer = vy;
@@ -1106,19 +1097,39 @@ __device__ __forceinline__ bool car_euler_fast(float4 p, const ChildCtl& ctl, co
     return aliveF > 0.0f;
 }
 
-// reference statePropagator.cu:5-76: controls, then the Euler loop (k_expand's form).
-template <int OBS, typename MidHook = NoMidHook>
-__device__ __forceinline__ bool propagate_car(float4 p, Xorwow& rs, const KgmtDev& d, const float4* obs,
-                                              ChildOut& out, MidHook midHook = MidHook()) {
-    const ChildCtl c = draw_controls<0>(rs, d);
-    return car_euler<OBS>(p, c, d, obs, out, midHook);
+// The one entry to the fast loop, for a wave whose call site found AGENT == 0, a register
+// list and car_fast_ok(d): the per-step schedule, wave_cull where the schedule does not
+// cover the wave, then the loop's form per wave (Payne-Hanek only if some lane's theta may
+// leave Cody-Waite's range: a huge steering tan can drive it there within a child) and per
+// plan (L = 1: one multiply less per step).  Every lane runs it; act drops the result of
+// lanes past S.  oLane: box (lane % n) of the register list (car_schedule).
+template <int OBS>
+__device__ __forceinline__ bool car_propagate_fast(float4 p, int parent, bool act, const ChildCtl& ctl,
+                                                   const KgmtDev& d, const float4* obs, float4 oLane, ChildOut& out) {
+    const StepSched sched = car_schedule<OBS>(p, parent, act, d, oLane);
+    WaveCull cull{~0u, true};   // the schedule covers the whole reach
+    if (!sched.valid) cull = car_cull<OBS>(p, ctl, d, obs);
+    bool alive;
+    if (__ballot(!car_theta_bounded(p, ctl, d)) != 0ull)   // rare
+        alive = car_euler_fast<OBS, true>(p, ctl, d, obs, cull, sched, out);
+    else if (d.invAgentLength == 1.0f)   // uniform
+        alive = car_euler_fast<OBS, false, true>(p, ctl, d, obs, cull, sched, out);
+    else
+        alive = car_euler_fast<OBS, false>(p, ctl, d, obs, cull, sched, out);
+    return alive && act;
 }
 
-template <int OBS, typename MidHook = NoMidHook>
+// reference statePropagator.cu:5-76: controls, then the Euler loop (k_expand's form).
+template <int OBS>
+__device__ __forceinline__ bool propagate_car(float4 p, Xorwow& rs, const KgmtDev& d, const float4* obs,
+                                              ChildOut& out) {
+    return car_euler<OBS>(p, draw_controls<0>(rs, d), d, obs, out);
+}
+
+template <int OBS>
 __device__ __forceinline__ bool propagate_point(float4 p, Xorwow& rs, const KgmtDev& d, const float4* obs,
-                                                ChildOut& out, MidHook midHook = MidHook()) {
-    const ChildCtl c = draw_controls<1>(rs, d);
-    return point_euler<OBS>(p, c, d, obs, out, midHook);
+                                                ChildOut& out) {
+    return point_euler<OBS>(p, draw_controls<1>(rs, d), d, obs, out);
 }
 
 }  // namespace sbmp

@@ -230,15 +230,7 @@ __global__ __launch_bounds__(kBlock) void k_expand(KgmtDev d, int t) {
             // box (lane % n) for the schedule: a load of its own (indexing ro[] by lane would put
             // the register list in scratch)
             const float4 oLane = G(d.obstacles)[lane % kRegObs];
-            const StepSched sched = car_schedule<OBS>(p, parent, act, d, oLane);
-            WaveCull cull{~0u, true};   // the schedule covers the whole reach
-            if (!sched.valid) cull = car_cull<OBS>(p, ctl, d, obs);
-            if (__ballot(!car_theta_bounded(p, ctl, d)) != 0ull)   // rare: Payne-Hanek per lane
-                valid = car_euler_fast<OBS, true>(p, ctl, d, obs, cull, sched, out) && act;
-            else if (d.invAgentLength == 1.0f)
-                valid = car_euler_fast<OBS, false, true>(p, ctl, d, obs, cull, sched, out) && act;
-            else
-                valid = car_euler_fast<OBS, false>(p, ctl, d, obs, cull, sched, out) && act;
+            valid = car_propagate_fast<OBS>(p, parent, act, ctl, d, obs, oLane, out);
         }
     }
     if (act) {
@@ -2424,8 +2416,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) voi
     if constexpr (AGENT == 0 && kRegObs > 0) {
         fast = car_fast_ok(d);   // per plan (uniform)
         if (fast) {
-            // a huge steering tan can drive theta past Cody-Waite's range within a child
-            const StepSched sched = car_schedule<OBS>(p, parent, act, d, oLane);
 #if SBMP_VALU_DUP == 3   // diagnostics: the schedule and the theta bound once more, on opaque copies
             {
                 float4 p2 = p;
@@ -2435,22 +2425,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) voi
                 asm volatile("" ::"s"(s2.boxes), "s"(s2.bounds), "s"(tb));
             }
 #endif
-            WaveCull cull{~0u, true};   // the schedule covers the whole reach
-            if (!sched.valid) cull = car_cull<OBS>(p, ctl, d, obs);
-            if (__ballot(!car_theta_bounded(p, ctl, d)) != 0ull)   // rare: Payne-Hanek per lane
-                valid = car_euler_fast<OBS, true>(p, ctl, d, obs, cull, sched, out) && act;
-            else if (d.invAgentLength == 1.0f)   // per plan (uniform): L = 1, one multiply less per step
-                valid = car_euler_fast<OBS, false, true>(p, ctl, d, obs, cull, sched, out) && act;
-            else
-                valid = car_euler_fast<OBS, false>(p, ctl, d, obs, cull, sched, out) && act;
+            valid = car_propagate_fast<OBS>(p, parent, act, ctl, d, obs, oLane, out);
         }
     }
     if (!fast) {
         out = ChildOut{};   // inactive lanes: defined values (the fast loop writes every lane)
         if (act)
-            valid = (AGENT == 0)
-                        ? car_euler<OBS, NoMidHook, OBS == kObsGrid>(p, ctl, d, obs, out, NoMidHook(), sGridStart)
-                        : point_euler<OBS, NoMidHook, OBS == kObsGrid>(p, ctl, d, obs, out, NoMidHook(), sGridStart);
+            valid = (AGENT == 0) ? car_euler<OBS, OBS == kObsGrid>(p, ctl, d, obs, out, sGridStart)
+                                 : point_euler<OBS, OBS == kObsGrid>(p, ctl, d, obs, out, sGridStart);
     }
     SBMP_STAMP(3);
 
@@ -2840,159 +2822,110 @@ static void launch(K kernel, dim3 grid, dim3 block, size_t shm, hipStream_t s, c
         hipLaunchKernelGGL(kernel, grid, block, shm, s, args...);
 }
 
-template <int AGENT>
-static void launch_expand_reg(const KgmtDev& d, int t, dim3 grid, dim3 block, hipStream_t s, const KernelTiming& tm) {
-    switch (d.nObs) {   // the box count is a compile-time constant of the register path
-        case 0: launch(k_expand<AGENT, kObsReg + 0>, grid, block, 0, s, tm, d, t); break;
-        case 1: launch(k_expand<AGENT, kObsReg + 1>, grid, block, 0, s, tm, d, t); break;
-        case 2: launch(k_expand<AGENT, kObsReg + 2>, grid, block, 0, s, tm, d, t); break;
-        case 3: launch(k_expand<AGENT, kObsReg + 3>, grid, block, 0, s, tm, d, t); break;
-        case 4: launch(k_expand<AGENT, kObsReg + 4>, grid, block, 0, s, tm, d, t); break;
-        case 5: launch(k_expand<AGENT, kObsReg + 5>, grid, block, 0, s, tm, d, t); break;
-        case 6: launch(k_expand<AGENT, kObsReg + 6>, grid, block, 0, s, tm, d, t); break;
-        case 7: launch(k_expand<AGENT, kObsReg + 7>, grid, block, 0, s, tm, d, t); break;
-        default: launch(k_expand<AGENT, kObsReg + 8>, grid, block, 0, s, tm, d, t); break;
+// The obstacle form a plan runs (variant: kgmt_launch.h), decided here and nowhere else:
+// f is called with the form as a compile-time constant.
+template <int OBS>
+using ObsForm = std::integral_constant<int, OBS>;
+
+template <typename F>
+static auto with_obs_form(const KgmtDev& d, int variant, F f) {
+    if (d.gridStart) return f(ObsForm<kObsGrid>{});   // the planner built the grid index (large lists, or variant 4)
+    if (d.nObs > kMaxLdsObs) return f(ObsForm<kObsGlobal>{});
+    if (d.nObs <= kMaxRegObs && (variant == 0 || variant == 3)) {
+        switch (d.nObs) {   // the box count is a compile-time constant of the register path
+            case 0: return f(ObsForm<kObsReg + 0>{});
+            case 1: return f(ObsForm<kObsReg + 1>{});
+            case 2: return f(ObsForm<kObsReg + 2>{});
+            case 3: return f(ObsForm<kObsReg + 3>{});
+            case 4: return f(ObsForm<kObsReg + 4>{});
+            case 5: return f(ObsForm<kObsReg + 5>{});
+            case 6: return f(ObsForm<kObsReg + 6>{});
+            case 7: return f(ObsForm<kObsReg + 7>{});
+            default: return f(ObsForm<kObsReg + 8>{});
+        }
     }
+    if (variant == 2) return f(ObsForm<kObsLds4>{});
+    return f(ObsForm<kObsLds>{});
 }
 
-template <int AGENT>
-static void launch_expand_agent(const KgmtDev& d, int t, int blocks, int variant, hipStream_t s,
-                                const KernelTiming& tm) {
-    const size_t shm = sizeof(float4) * (size_t)d.nObs;
-    const dim3 grid(blocks), block(kBlock);
-    if (d.gridStart) {   // the planner built the grid index (large lists, or variant 4)
-        launch(k_expand<AGENT, kObsGrid>, grid, block, 0, s, tm, d, t);
-    } else if (d.nObs > kMaxLdsObs) {
-        launch(k_expand<AGENT, kObsGlobal>, grid, block, 0, s, tm, d, t);
-    } else if (d.nObs <= kMaxRegObs && (variant == 0 || variant == 3)) {
-        launch_expand_reg<AGENT>(d, t, grid, block, s, tm);
-    } else if (variant == 2) {
-        launch(k_expand<AGENT, kObsLds4>, grid, block, shm, s, tm, d, t);
-    } else {
-        launch(k_expand<AGENT, kObsLds>, grid, block, shm, s, tm, d, t);
-    }
+int obstacle_form(const KgmtDev& d, int variant) {
+    return with_obs_form(d, variant, [](auto obs) { return obs.value >= kObsReg ? kObsReg : obs.value; });
+}
+
+// dynamic LDS of a form's obstacle list (the two LDS forms stage it per workgroup)
+static size_t obs_lds_bytes(const KgmtDev& d, int obs) {
+    return (obs == kObsLds || obs == kObsLds4) ? sizeof(float4) * (size_t)d.nObs : 0;
 }
 
 void launch_expand(const KgmtDev& d, int t, int agent, int blocks, int variant, hipStream_t s,
                    const KernelTiming& tm) {
-    if (agent == 0) launch_expand_agent<0>(d, t, blocks, variant, s, tm);
-    else launch_expand_agent<1>(d, t, blocks, variant, s, tm);
+    const dim3 grid(blocks), block(kBlock);
+    with_obs_form(d, variant, [&](auto obs) {
+        const size_t shm = obs_lds_bytes(d, obs.value);   // k_expand reads the grid's cell starts from global memory
+        if (agent == 0) launch(k_expand<0, obs.value>, grid, block, shm, s, tm, d, t);
+        else launch(k_expand<1, obs.value>, grid, block, shm, s, tm, d, t);
+    });
 }
 
-// k_step's dynamic LDS past the obstacle list: the block (row) prefix and the R2New bits;
-// on a sharded rank also the u16 block counts of every row, 16-B aligned (the kernel's
-// sC16 / sGridStart layout).
-static size_t step_lds_bytes(const KgmtDev& d, bool sh) {
+// k_step's dynamic LDS for obstacle form obs, in the kernel's layout:
+// [LDS obstacles][block (row) prefix: scan entries + 1 ints][R2New bits: nR2 / 32 words]
+// (sharded: [16-B aligned u16 block counts of every row: sC16]) [grid cell starts: sGridStart]
+static size_t step_lds_bytes(const KgmtDev& d, int obs) {
+    const bool sh = d.sharded;
     const size_t nS = sh ? d.nBlocks / d.nranks : d.nBlocks;   // scan entries: blocks, or rows
-    size_t b = sizeof(int) * (nS + 1) + sizeof(uint32_t) * (size_t)(d.nR2 / 32);
+    // (the obstacle list is whole float4s, so the 16-B alignment below is the same with or without it)
+    size_t b = obs_lds_bytes(d, obs) + sizeof(int) * (nS + 1) + sizeof(uint32_t) * (size_t)(d.nR2 / 32);
     if (sh) b = ((b + 15) & ~(size_t)15) + (d.c16Lds ? sizeof(uint16_t) * (((size_t)d.nBlocks + 7) & ~(size_t)7) : 0);
+    if (obs == kObsGrid) b += sizeof(int) * ((size_t)d.gridG * d.gridG + 1);
     return b;
 }
 
-template <int AGENT, bool SH>
-static void launch_step_form(const KgmtDev& d, int t, int expand, int variant, hipStream_t s,
-                             const KernelTiming& tm) {
-    // dynamic LDS: [LDS obstacles][block prefix: nBlocks + 1 ints][R2New bits: nR2 / 32 words]
-    // (sharded: [16-B aligned u16 block counts]) [grid cell starts]
-    const size_t pfx = step_lds_bytes(d, SH);
-    const size_t shm = sizeof(float4) * (size_t)d.nObs + pfx;   // LDS obstacle forms
-    const size_t gridLds = d.gridStart ? sizeof(int) * ((size_t)d.gridG * d.gridG + 1) : 0;   // + the cell starts
-    const int blocks = SH ? d.nBlocks / d.nranks : d.nBlocks;
-    const dim3 grid(1 + blocks), block(kBlock);   // workgroup 0 plans, 1.. expand
-    long long* const tlBase = (d.timeline && t == d.timelineIter && expand) ? d.timeline : nullptr;
-    const int4* const cnt4 = SH ? reinterpret_cast<const int4*>(d.stepXr + d.xRowOff)
-                                : reinterpret_cast<const int4*>(d.stepCnt + (size_t)((t - 1) & 1) * kMaxStepBlocks);
-#define SBMP_STEP_ARGS                                                                                        \
-    d.devSelf, (int)((unsigned)t | ((unsigned)(expand != 0) << 31)), SH ? (d.rank | (d.nranks << 8)) : (1 << 8),  \
-        cnt4, d.ctrl + (t - 1), d.rngA, d.rngB, d.gnewOut, d.status, tlBase, SH ? d.nBlocks / d.nranks : d.nBlocks, \
-        SH ? reinterpret_cast<const int*>(d.stepXr + d.xCntOff) : nullptr
-    if (d.gridStart) {
-        launch(k_step<AGENT, kObsGrid, SH>, grid, block, pfx + gridLds, s, tm, SBMP_STEP_ARGS);
-    } else if (d.nObs > kMaxLdsObs) {
-        launch(k_step<AGENT, kObsGlobal, SH>, grid, block, pfx, s, tm, SBMP_STEP_ARGS);
-    } else if (d.nObs <= kMaxRegObs && (variant == 0 || variant == 3)) {
-        switch (d.nObs) {
-            case 0: launch(k_step<AGENT, kObsReg + 0, SH>, grid, block, pfx, s, tm, SBMP_STEP_ARGS); break;
-            case 1: launch(k_step<AGENT, kObsReg + 1, SH>, grid, block, pfx, s, tm, SBMP_STEP_ARGS); break;
-            case 2: launch(k_step<AGENT, kObsReg + 2, SH>, grid, block, pfx, s, tm, SBMP_STEP_ARGS); break;
-            case 3: launch(k_step<AGENT, kObsReg + 3, SH>, grid, block, pfx, s, tm, SBMP_STEP_ARGS); break;
-            case 4: launch(k_step<AGENT, kObsReg + 4, SH>, grid, block, pfx, s, tm, SBMP_STEP_ARGS); break;
-            case 5: launch(k_step<AGENT, kObsReg + 5, SH>, grid, block, pfx, s, tm, SBMP_STEP_ARGS); break;
-            case 6: launch(k_step<AGENT, kObsReg + 6, SH>, grid, block, pfx, s, tm, SBMP_STEP_ARGS); break;
-            case 7: launch(k_step<AGENT, kObsReg + 7, SH>, grid, block, pfx, s, tm, SBMP_STEP_ARGS); break;
-            default: launch(k_step<AGENT, kObsReg + 8, SH>, grid, block, pfx, s, tm, SBMP_STEP_ARGS); break;
-        }
-    } else if (variant == 2) {
-        launch(k_step<AGENT, kObsLds4, SH>, grid, block, shm, s, tm, SBMP_STEP_ARGS);
-    } else {
-        launch(k_step<AGENT, kObsLds, SH>, grid, block, shm, s, tm, SBMP_STEP_ARGS);
-    }
-#undef SBMP_STEP_ARGS
-}
-
-// The k_step instantiation launch_step_form picks, and its dynamic LDS, for the
-// residency check (step_resident_groups).
-using StepFn = void (*)(const KgmtDev*, int, int, const int4*, const IterCtrl*, const uint4*, const uint2*,
-                        const unsigned long long*, const PlannerStatus*, long long*, int, const int*);
-template <int AGENT, bool SH>
-static StepFn step_fn(const KgmtDev& d, int variant, size_t* shm) {
-    const size_t pfx = step_lds_bytes(d, SH);
-    *shm = pfx;
-    if (d.gridStart) {
-        *shm = pfx + sizeof(int) * ((size_t)d.gridG * d.gridG + 1);   // + the cell-start table (k_step stages it)
-        return k_step<AGENT, kObsGrid, SH>;
-    }
-    if (d.nObs > kMaxLdsObs) return k_step<AGENT, kObsGlobal, SH>;
-    if (d.nObs <= kMaxRegObs && (variant == 0 || variant == 3)) {
-        switch (d.nObs) {
-            case 0: return k_step<AGENT, kObsReg + 0, SH>;
-            case 1: return k_step<AGENT, kObsReg + 1, SH>;
-            case 2: return k_step<AGENT, kObsReg + 2, SH>;
-            case 3: return k_step<AGENT, kObsReg + 3, SH>;
-            case 4: return k_step<AGENT, kObsReg + 4, SH>;
-            case 5: return k_step<AGENT, kObsReg + 5, SH>;
-            case 6: return k_step<AGENT, kObsReg + 6, SH>;
-            case 7: return k_step<AGENT, kObsReg + 7, SH>;
-            default: return k_step<AGENT, kObsReg + 8, SH>;
-        }
-    }
-    *shm = sizeof(float4) * (size_t)d.nObs + pfx;   // LDS obstacle forms
-    return (variant == 2) ? k_step<AGENT, kObsLds4, SH> : k_step<AGENT, kObsLds, SH>;
+// The k_step instantiation of a plan and its dynamic LDS: what launch_step launches is
+// what step_resident_groups asked the occupancy query about.
+using StepFn = decltype(&k_step<0, kObsGlobal, false>);
+struct StepKernel {
+    StepFn fn;
+    size_t lds;
+};
+static StepKernel step_kernel(const KgmtDev& d, int agent, int variant) {
+    return with_obs_form(d, variant, [&](auto obs) {
+        const StepFn fn = (agent == 0) ? (d.sharded ? k_step<0, obs.value, true> : k_step<0, obs.value, false>)
+                                       : (d.sharded ? k_step<1, obs.value, true> : k_step<1, obs.value, false>);
+        return StepKernel{fn, step_lds_bytes(d, obs.value)};
+    });
 }
 
 int step_resident_groups(const KgmtDev& d, int agent, int variant, StepResidency* why) {
-    size_t shm = 0;
-    StepFn fn;
-    if (agent == 0) fn = d.sharded ? step_fn<0, true>(d, variant, &shm) : step_fn<0, false>(d, variant, &shm);
-    else fn = d.sharded ? step_fn<1, true>(d, variant, &shm) : step_fn<1, false>(d, variant, &shm);
+    const StepKernel k = step_kernel(d, agent, variant);
     int dev = 0, cus = 0, perCU = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (shm > 65536)   // LDS above 64 KB needs the opt-in (not reached by k_step's forms, kept for safety)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)shm);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, reinterpret_cast<const void*>(fn), kBlock, shm) !=
+    if (k.lds > 65536)   // LDS above 64 KB needs the opt-in (not reached by k_step's forms, kept for safety)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)k.lds);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, reinterpret_cast<const void*>(k.fn), kBlock, k.lds) !=
         hipSuccess)
         return 0;
     if (why) {
         why->perCU = perCU;
         why->cus = cus;
-        why->dynLds = (long long)shm;
+        why->dynLds = (long long)k.lds;
     }
     return perCU * cus;
 }
 
-template <int AGENT>
-static void launch_step_agent(const KgmtDev& d, int t, int expand, int variant, hipStream_t s,
-                              const KernelTiming& tm) {
-    if (d.sharded) launch_step_form<AGENT, true>(d, t, expand, variant, s, tm);
-    else launch_step_form<AGENT, false>(d, t, expand, variant, s, tm);
-}
-
 void launch_step(const KgmtDev& d, int t, int expand, int agent, int variant, hipStream_t s,
                  const KernelTiming& tm) {
-    if (agent == 0) launch_step_agent<0>(d, t, expand, variant, s, tm);
-    else launch_step_agent<1>(d, t, expand, variant, s, tm);
+    const StepKernel k = step_kernel(d, agent, variant);
+    const bool sh = d.sharded;
+    const int blocks = sh ? d.nBlocks / d.nranks : d.nBlocks;
+    const dim3 grid(1 + blocks), block(kBlock);   // workgroup 0 plans, 1.. expand
+    long long* const tlBase = (d.timeline && t == d.timelineIter && expand) ? d.timeline : nullptr;
+    const int4* const cnt4 = sh ? reinterpret_cast<const int4*>(d.stepXr + d.xRowOff)
+                                : reinterpret_cast<const int4*>(d.stepCnt + (size_t)((t - 1) & 1) * kMaxStepBlocks);
+    launch(k.fn, grid, block, k.lds, s, tm, d.devSelf, (int)((unsigned)t | ((unsigned)(expand != 0) << 31)),
+           sh ? (d.rank | (d.nranks << 8)) : (1 << 8), cnt4, d.ctrl + (t - 1), d.rngA, d.rngB, d.gnewOut, d.status,
+           tlBase, blocks, sh ? reinterpret_cast<const int*>(d.stepXr + d.xCntOff) : nullptr);
 }
 
 void launch_fold_r2(const KgmtDev& d, int tFirst, int tLast, hipStream_t s, const KernelTiming& tm) {

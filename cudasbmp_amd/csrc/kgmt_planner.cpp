@@ -745,10 +745,11 @@ void KgmtPlanner::choose_form(const float* d_obstacles, int nObs) {
 void KgmtPlanner::path_info(sbmp_path_info* out) {
     const KgmtDev& d = d_;
     out->stepForm = d.stepMode ? 1 : 0;
-    out->obstacleForm = d.gridStart                    ? SBMP_OBS_GRID
-                        : d.nObs > kMaxLdsObs           ? SBMP_OBS_GLOBAL
-                        : (d.nObs <= kMaxRegObs && (expandVariant_ == 0 || expandVariant_ == 3)) ? SBMP_OBS_REGISTERS
-                                                        : SBMP_OBS_LDS;
+    const int form = obstacle_form(d, expandVariant_);
+    out->obstacleForm = form == kObsGrid     ? SBMP_OBS_GRID
+                        : form == kObsGlobal ? SBMP_OBS_GLOBAL
+                        : form == kObsReg    ? SBMP_OBS_REGISTERS
+                                             : SBMP_OBS_LDS;
     out->residentGroups = residentGroups_;
     out->neededGroups = neededGroups_;
     out->exchange = !d.sharded ? SBMP_EXCHANGE_NONE : (oneshot_ ? SBMP_EXCHANGE_ONESHOT : SBMP_EXCHANGE_COLLECTIVE);

@@ -242,7 +242,7 @@ def _build() -> list:
         dict(width=30.0, height=12.0), lambda: random_boxes(600, 30.0, 12.0, 7, 0.3, 0.8, nan_planted),
         goal=(27.0, 10.0), env={"SBMP_EXPAND_VARIANT": "4"}, obstacle_form="grid", cover=changes, added_rows=(0,))
 
-    # ---- G. forms: k_expand's own copy of the fast-loop dispatch (SBMP_STEP=0), shard groups
+    # ---- G. forms: the two-launch form's call into the same fast loop (k_expand, SBMP_STEP=0), shard groups
     by_name = {s.name: s for s in S}
 
     def again(src, suffix, targets, **changes_):
