@@ -6,6 +6,11 @@ tests/test_scenarios_oracle.py proves on the CPU oracle alone that a scenario
 reaches its edge (its `cover` conditions); tests/test_gpu_scenarios.py compares
 the HIP planner with the oracle bit for bit on the same table.
 
+Family F's F-touching-root / F-touching-root-next test one box comparison at equality;
+they are now one of a full set, family H ("verdict edges": every comparison and both
+movable walls, in every obstacle form), which needs an oracle pass to build its boxes
+and so has its own module, tests/edge_scenarios.py.
+
 Plain numpy: no GPU and no oracle at import.
 """
 from __future__ import annotations
@@ -204,6 +209,10 @@ def _build() -> list:
             dict(numDisc=disc), lambda boxes=boxes: demo_prefix(boxes), initial=root, seed=seed, cover=sched)
 
     # ---- F. degenerate boxes (registers): the obsNaN fallback, the predicates at equality
+    #      (F-touching-root / -next is one comparison, o.z <= minx, at the root, in the register fast loop;
+    #      the full set -- all four comparisons and both movable walls, at equality and one ulp either
+    #      side, in every obstacle form -- is family H, tests/edge_scenarios.py, which derives its boxes
+    #      from an oracle pass and so lives outside this oracle-free module)
     nan = float("nan")
     inf = float("inf")
     nan_low = (nan, 4.0, 7.0, 4.5)
