@@ -93,6 +93,11 @@ class PathInfo(ctypes.Structure):   # sbmp_path_info
                                             "fusedExchange", "oneshotCheck", "mirrorCheck", "fusedCheck", "rowTableLds")]
 
 
+class BatchInfo(ctypes.Structure):   # sbmp_batch_info
+    _fields_ = [(n, ctypes.c_int) for n in ("count", "groupsPerMember", "residentGroups", "membersPerLaunch",
+                                            "launchesPerIteration", "batched")]
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", ctypes.c_longlong), ("totalMs", ctypes.c_double)]
 
@@ -111,6 +116,9 @@ EXPORTED_SYMBOLS = (
     "sbmp_device_alloc", "sbmp_device_copy_to", "sbmp_device_copy_from", "sbmp_kgmt_set_iteration_dump",
     "sbmp_load_system_config",
     "sbmp_obstacle_grid_query", "sbmp_kgmt_solution_path", "sbmp_random_tree", "sbmp_hbm_copy_bandwidth",
+    "sbmp_kgmt_batch_create", "sbmp_kgmt_batch_destroy", "sbmp_kgmt_batch_plan", "sbmp_kgmt_batch_begin",
+    "sbmp_kgmt_batch_step", "sbmp_kgmt_batch_enqueue", "sbmp_kgmt_batch_sync", "sbmp_kgmt_batch_result",
+    "sbmp_kgmt_batch_member", "sbmp_kgmt_batch_info", "sbmp_kgmt_batch_kernel_stat", "sbmp_batch_pack",
 )
 
 _lib = None
@@ -181,6 +189,18 @@ def lib():
         "sbmp_device_free": [vp],
         "sbmp_device_count": [P(i)],
         "sbmp_hbm_copy_bandwidth": [ctypes.c_size_t, i, P(ctypes.c_double)],
+        "sbmp_kgmt_batch_create": [P(KgmtParams), i, P(vp)],
+        "sbmp_kgmt_batch_destroy": [vp],
+        "sbmp_kgmt_batch_plan": [vp, vp, vp, vp, i, vp, vp],
+        "sbmp_kgmt_batch_begin": [vp, vp, vp, vp, i, vp],
+        "sbmp_kgmt_batch_step": [vp, i, P(i)],
+        "sbmp_kgmt_batch_enqueue": [vp, i],
+        "sbmp_kgmt_batch_sync": [vp],
+        "sbmp_kgmt_batch_result": [vp, i, P(PlanResult)],
+        "sbmp_kgmt_batch_member": [vp, i, P(vp)],
+        "sbmp_kgmt_batch_info": [vp, P(BatchInfo)],
+        "sbmp_kgmt_batch_kernel_stat": [vp, P(KernelStat)],
+        "sbmp_batch_pack": [vp, i, i, vp, P(i)],
     }
     for name, args in sig.items():
         f = getattr(L, name)

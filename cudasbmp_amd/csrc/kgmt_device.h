@@ -245,6 +245,26 @@ struct KgmtDev {
     const KgmtDev* devSelf;
 };
 
+// One member of a k_step_batch launch: what k_step's twelve arguments are
+// made of for that member, and its workgroup count (1 + blocks).  Nothing in it changes
+// during a plan: the launch passes t | expand << 31 as a kernel argument, and the two
+// arguments that depend on the iteration are derived from it in the kernel (cnt4 = parity
+// (t - 1) & 1 of stepCnt, ctrlPrev = ctrl + t - 1), so the host writes the table once per
+// begin() and no copy sits between two launches.  Workgroup (x, y) reads record y with
+// scalar loads.
+struct alignas(16) StepBatchRec {
+    const KgmtDev* dev;
+    const int* stepCnt;       // [2][kMaxStepBlocks] packed block counts
+    const IterCtrl* ctrl;     // ctrl[0 .. numIterations + 1]
+    const uint4* rngA;
+    const uint2* rngB;
+    const unsigned long long* gnew;
+    const PlannerStatus* status;
+    int groups;               // 1 + blocks: workgroups x >= groups of row y return at entry
+    int pad;
+};
+static_assert(sizeof(StepBatchRec) == 64, "StepBatchRec: four 16-B scalar loads");
+
 // Global-address-space view of a device pointer.  A pointer loaded from the plan
 // struct in device memory (k_step reads it there) is generic to the compiler: its
 // accesses become flat_* instructions, which take no scalar base, count against

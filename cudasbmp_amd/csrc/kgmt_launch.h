@@ -36,6 +36,15 @@ struct StepResidency {   // the query's terms, for the message when k_step does 
     long long dynLds = 0;
 };
 int step_resident_groups(const KgmtDev& d, int agent, int variant, StepResidency* why = nullptr);
+// k_step_batch: k_step(t) of several unsharded plans of one form in one launch (grid
+// maxGroups x members; table: `members` records in device memory, written once per
+// begin(): step_batch_record fills one on the host).  step_batch_resident_groups is the
+// occupancy query on that instantiation itself at d's dynamic LDS: the sum of the
+// members' 1 + blocks must not exceed it.  0 if the query fails or d is sharded.
+int step_batch_resident_groups(const KgmtDev& d, int agent, int variant, StepResidency* why = nullptr);
+void step_batch_record(const KgmtDev& d, StepBatchRec* r);
+void launch_step_batch(const KgmtDev& d, int t, int expand, int agent, int variant, const StepBatchRec* table,
+                       int members, int maxGroups, hipStream_t s, const KernelTiming& tm = KernelTiming());
 void launch_fold_r2(const KgmtDev& d, int tFirst, int tLast, hipStream_t s, const KernelTiming& tm = KernelTiming());
 // k_finish(t): insert iteration t (insertBlocks = every global 256-slot block) +
 // prepare iteration t+1.  t = 0 prepares iteration 1 only (insertBlocks = 0).

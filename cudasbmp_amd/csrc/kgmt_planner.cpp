@@ -82,7 +82,7 @@ static float markstein_rcp(float b) {
 }
 
 // PlannerStatus::error -> the bounded wait that gave up (kgmt_device.h kErr*).
-[[noreturn]] static void throw_wait_error(int e) {
+[[noreturn]] void throw_wait_error(int e) {
     if (e == kErrExchange)
         throw Error(SBMP_ERR_COMM, "k_oneshot: a peer rank's exchange flag did not arrive within 20 s");
     if (e == kErrStepHandoff)

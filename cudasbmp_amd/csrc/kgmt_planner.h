@@ -166,6 +166,7 @@ public:
     int rank() const { return d_.rank; }
 
 private:
+    friend class BatchGroup;   // drives its members' k_step launches as one k_step_batch (kgmt_batch.cpp)
     enum KernelId { K_EXPAND = 0, K_FINISH, K_FOLD, K_PACK, K_STEP, K_XCHG, K_COUNT };
     KernelTiming timing(int id);
     void collect_events();
@@ -297,6 +298,70 @@ private:
     hipStream_t stream_ = nullptr;
     std::vector<KgmtPlanner*> ranks_;
 };
+
+// Several independent single-rank plans (one parameter set, one obstacle list; their own
+// roots, goals and seeds) on ONE device and one stream, one k_step_batch launch per
+// iteration for as many members as the device holds at once.  Each
+// member is a whole KgmtPlanner (its own buffers, RNG, control blocks, poll word), so
+// every export of a member reads as a single planner's would.
+class BatchGroup {
+public:
+    BatchGroup(const sbmp_kgmt_params& p, int count);
+    ~BatchGroup();
+    BatchGroup(const BatchGroup&) = delete;
+    BatchGroup& operator=(const BatchGroup&) = delete;
+
+    int count() const { return (int)members_.size(); }
+    KgmtPlanner& member(int i);
+    // initials / goals: count x 7 floats; seeds: count
+    void begin(const float* initials, const float* goals, const float* d_obstacles, int nObs, const uint64_t* seeds);
+    void enqueue(int iterations);   // every member advances by up to `iterations`
+    void sync();                    // flush passes, then the stream
+    void fold_pending();
+    int active();                   // syncs; members whose loop has not ended
+    void run_plan();                // until every member has ended (goal, full tree, numIterations)
+    void result(int i, sbmp_plan_result* r);
+    void info(sbmp_batch_info* out) const;
+    sbmp_kernel_stat kernel_stat();   // "k_step_batch": launches timed with profileKernels
+    hipStream_t stream() const { return stream_; }
+
+    // Members in index order into the fewest launches whose workgroups (the sum of the
+    // members' groups) stay within residentGroups; launchOfMember[i] = -1 for a member
+    // that does not fit alone.  Returns the number of launches.  Host-only.
+    static int pack(const int* groupsPerMember, int count, int residentGroups, int* launchOfMember);
+
+private:
+    struct Launch {
+        int first = 0, members = 0, maxGroups = 0;
+        StepBatchRec* dTable = nullptr;   // device, `members` records, written at begin()
+        StepBatchRec* stage = nullptr;    // pinned: what was last copied there
+    };
+    void issue(int t, int expand);        // the batch launches of iteration t (or its flush pass)
+    void flush();
+    void stage_member(KgmtPlanner* k, int t);   // a member's own launches of iteration t
+    int min_seen() const;
+    KernelTiming timing();
+    void collect_events();
+    void free_launches();
+
+    sbmp_kgmt_params p_;
+    hipStream_t stream_ = nullptr;
+    std::vector<KgmtPlanner*> members_;
+    std::vector<Launch> launches_;
+    std::vector<int> launchOf_;
+    bool begun_ = false, batched_ = false;
+    int residentGroups_ = 0, groupsPerMember_ = 0, membersPerLaunch_ = 0;
+    struct Pending {
+        hipEvent_t a, b;
+    };
+    std::vector<Pending> pending_;
+    std::vector<hipEvent_t> eventPool_;
+    long long statLaunches_ = 0;
+    double statMs_ = 0.0;
+};
+
+// PlannerStatus::error -> the bounded wait that gave up (throws).
+[[noreturn]] void throw_wait_error(int e);
 
 double now_ms();
 

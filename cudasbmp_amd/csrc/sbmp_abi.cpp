@@ -18,6 +18,12 @@ using sbmp::Planner;
 struct sbmp_kgmt {
     Planner* planner = nullptr;
     sbmp::Exchange* comm = nullptr;   // sharded: owned collectives (kgmt_sharded.cpp)
+    bool borrowed = false;            // a batch member (sbmp_kgmt_batch_member): the batch plans and owns it
+};
+
+struct sbmp_kgmt_batch {
+    sbmp::BatchGroup* group = nullptr;
+    std::vector<sbmp_kgmt> views;     // one borrowed handle per member
 };
 
 namespace sbmp {
@@ -195,6 +201,7 @@ sbmp_status sbmp_comm_get_unique_id(uint8_t id[SBMP_COMM_ID_BYTES]) {
 sbmp_status sbmp_kgmt_destroy(sbmp_kgmt* h) {
     return guarded([&] {
         if (!h) return;
+        if (h->borrowed) throw Error(SBMP_ERR_STATE, "a batch member is destroyed with its batch");
         delete h->planner;
         delete h->comm;
         delete h;
@@ -204,11 +211,17 @@ sbmp_status sbmp_kgmt_destroy(sbmp_kgmt* h) {
 #define PLANNER(h)                                                     \
     REQUIRE((h) && (h)->planner, "NULL planner handle");               \
     Planner& P = *(h)->planner
+// planning calls: a batch member's iterations are driven by its batch
+#define OWNED(h)                                                                                        \
+    do {                                                                                                \
+        if ((h)->borrowed) throw Error(SBMP_ERR_STATE, "a batch member is planned through its batch"); \
+    } while (0)
 
 sbmp_status sbmp_kgmt_begin(sbmp_kgmt* h, const float initial[7], const float goal[7], const float* d_obstacles,
                             int obstaclesCount, uint64_t seed) {
     return guarded([&] {
         PLANNER(h);
+        OWNED(h);
         P.begin(initial, goal, d_obstacles, obstaclesCount, seed);
     });
 }
@@ -217,6 +230,7 @@ sbmp_status sbmp_kgmt_plan(sbmp_kgmt* h, const float initial[7], const float goa
                            int obstaclesCount, uint64_t seed, sbmp_plan_result* result) {
     return guarded([&] {
         PLANNER(h);
+        OWNED(h);
         P.begin(initial, goal, d_obstacles, obstaclesCount, seed);
         // The planner's loop control (KgmtPlanner::run_plan): over-enqueued iterations of a
         // finished loop are no-ops, so they cost a few microseconds, not correctness.
@@ -228,6 +242,7 @@ sbmp_status sbmp_kgmt_plan(sbmp_kgmt* h, const float initial[7], const float goa
 sbmp_status sbmp_kgmt_step(sbmp_kgmt* h, int iterations, int* active) {
     return guarded([&] {
         PLANNER(h);
+        OWNED(h);
         REQUIRE(iterations >= 0, "iterations must be >= 0");
         P.enqueue(iterations);
         const bool a = P.active();
@@ -238,6 +253,7 @@ sbmp_status sbmp_kgmt_step(sbmp_kgmt* h, int iterations, int* active) {
 sbmp_status sbmp_kgmt_enqueue(sbmp_kgmt* h, int iterations) {
     return guarded([&] {
         PLANNER(h);
+        OWNED(h);
         REQUIRE(iterations >= 0, "iterations must be >= 0");
         P.enqueue(iterations);
     });
@@ -253,6 +269,7 @@ sbmp_status sbmp_kgmt_sync(sbmp_kgmt* h) {
 sbmp_status sbmp_kgmt_set_iteration_dump(sbmp_kgmt* h, const char* dir) {
     return guarded([&] {
         PLANNER(h);
+        if (h->borrowed) throw Error(SBMP_ERR_UNSUPPORTED, "per-iteration dumps are not supported in a batch");
         P.set_iteration_dump(dir ? std::string(dir) : std::string());
     });
 }
@@ -541,6 +558,131 @@ sbmp_status sbmp_hbm_copy_bandwidth(size_t bytes, int reps, double* gbs) {
         REQUIRE(gbs, "NULL output");
         *gbs = 0.0;
         *gbs = sbmp::hbm_copy_bandwidth(bytes, reps);
+    });
+}
+
+// ---------------------------------------------------------------- batches
+#define BATCH(h)                                                   \
+    REQUIRE((h) && (h)->group, "NULL batch handle");               \
+    sbmp::BatchGroup& B = *(h)->group
+
+sbmp_status sbmp_kgmt_batch_create(const sbmp_kgmt_params* p, int count, sbmp_kgmt_batch** out) {
+    return guarded([&] {
+        REQUIRE(p && out, "NULL argument");
+        *out = nullptr;
+        REQUIRE(count >= 1, "a batch needs at least one member");
+        sbmp_kgmt_batch* h = new sbmp_kgmt_batch;
+        try {
+            h->group = new sbmp::BatchGroup(*p, count);
+            h->views.resize(count);
+            for (int i = 0; i < count; ++i) {
+                h->views[i].planner = &h->group->member(i);
+                h->views[i].borrowed = true;
+            }
+        } catch (...) {
+            delete h->group;
+            delete h;
+            throw;
+        }
+        *out = h;
+    });
+}
+
+sbmp_status sbmp_kgmt_batch_destroy(sbmp_kgmt_batch* h) {
+    return guarded([&] {
+        if (!h) return;
+        delete h->group;
+        delete h;
+    });
+}
+
+sbmp_status sbmp_kgmt_batch_begin(sbmp_kgmt_batch* h, const float* initials, const float* goals,
+                                  const float* d_obstacles, int obstaclesCount, const uint64_t* seeds) {
+    return guarded([&] {
+        BATCH(h);
+        B.begin(initials, goals, d_obstacles, obstaclesCount, seeds);
+    });
+}
+
+sbmp_status sbmp_kgmt_batch_plan(sbmp_kgmt_batch* h, const float* initials, const float* goals,
+                                 const float* d_obstacles, int obstaclesCount, const uint64_t* seeds,
+                                 sbmp_plan_result* results) {
+    return guarded([&] {
+        BATCH(h);
+        B.begin(initials, goals, d_obstacles, obstaclesCount, seeds);
+        B.run_plan();
+        if (results)
+            for (int i = 0; i < B.count(); ++i) B.result(i, results + i);
+    });
+}
+
+sbmp_status sbmp_kgmt_batch_step(sbmp_kgmt_batch* h, int iterations, int* active) {
+    return guarded([&] {
+        BATCH(h);
+        REQUIRE(iterations >= 0, "iterations must be >= 0");
+        B.enqueue(iterations);
+        const int a = B.active();
+        if (active) *active = a;
+    });
+}
+
+sbmp_status sbmp_kgmt_batch_enqueue(sbmp_kgmt_batch* h, int iterations) {
+    return guarded([&] {
+        BATCH(h);
+        REQUIRE(iterations >= 0, "iterations must be >= 0");
+        B.enqueue(iterations);
+    });
+}
+
+sbmp_status sbmp_kgmt_batch_sync(sbmp_kgmt_batch* h) {
+    return guarded([&] {
+        BATCH(h);
+        B.sync();
+    });
+}
+
+sbmp_status sbmp_kgmt_batch_result(sbmp_kgmt_batch* h, int member, sbmp_plan_result* result) {
+    return guarded([&] {
+        BATCH(h);
+        REQUIRE(result, "NULL result");
+        B.result(member, result);
+    });
+}
+
+sbmp_status sbmp_kgmt_batch_member(sbmp_kgmt_batch* h, int i, sbmp_kgmt** borrowed) {
+    return guarded([&] {
+        BATCH(h);
+        REQUIRE(borrowed, "NULL output");
+        *borrowed = nullptr;
+        REQUIRE(i >= 0 && i < B.count(), "no such batch member");
+        *borrowed = &h->views[i];
+    });
+}
+
+sbmp_status sbmp_kgmt_batch_info(sbmp_kgmt_batch* h, sbmp_batch_info* out) {
+    return guarded([&] {
+        BATCH(h);
+        REQUIRE(out, "out must be non-NULL");
+        B.info(out);
+    });
+}
+
+sbmp_status sbmp_kgmt_batch_kernel_stat(sbmp_kgmt_batch* h, sbmp_kernel_stat* out) {
+    return guarded([&] {
+        BATCH(h);
+        REQUIRE(out, "out must be non-NULL");
+        *out = B.kernel_stat();
+    });
+}
+
+sbmp_status sbmp_batch_pack(const int* groupsPerMember, int count, int residentGroups, int* launchOfMember,
+                            int* launches) {
+    return guarded([&] {
+        REQUIRE(groupsPerMember && launchOfMember && launches, "NULL argument");
+        REQUIRE(count >= 1, "count must be >= 1");
+        REQUIRE(residentGroups >= 0, "residentGroups must be >= 0");
+        for (int i = 0; i < count; ++i) REQUIRE(groupsPerMember[i] >= 1, "a member has at least one workgroup");
+        *launches = sbmp::BatchGroup::pack(groupsPerMember, count, residentGroups, launchOfMember);
     });
 }
 

@@ -351,6 +351,60 @@ sbmp_status sbmp_kgmt_create_sharded(const sbmp_kgmt_params* p, const uint8_t id
  * (exports merge the ranks).  nranks = 1 gives a plain planner. */
 sbmp_status sbmp_kgmt_create_local_group(const sbmp_kgmt_params* p, int nranks, sbmp_kgmt** out);
 
+/* ---- Batches: several independent queries on one map, planned together on one GPU ----
+ * A batch holds `count` single-GPU planners with one parameter set on one stream.  The
+ * members take their own initial states, goals and seeds and share the obstacle list.
+ * While every member runs the one-launch form (sbmp_path_info.stepForm), an iteration of
+ * all members is one k_step_batch launch, or the fewest launches whose workgroups the
+ * device holds at once (a k_step workgroup waits in-kernel for its planner workgroup,
+ * so a launch never asks for more than the occupancy query gives; SBMP_BATCH_MAX_GROUPS=n
+ * lowers that figure).  Otherwise the members' own launches run in turn.  Every member
+ * computes exactly what sbmp_kgmt_plan computes for its query (no reference counterpart:
+ * the reference plans one query per KGMT object). */
+typedef struct sbmp_kgmt_batch sbmp_kgmt_batch;
+typedef struct sbmp_batch_info {
+    int count;                /* members */
+    int groupsPerMember;      /* 1 + 256-slot blocks: workgroups one member needs resident */
+    int residentGroups;       /* k_step_batch workgroups the device holds at once at the last begin
+                                 (occupancy x CUs, lowered by SBMP_BATCH_MAX_GROUPS); 0 before it */
+    int membersPerLaunch;     /* the most members in one launch (1 when the members run in turn) */
+    int launchesPerIteration; /* batch launches per iteration; `count` when the members run in turn */
+    int batched;              /* 1: iterations run as k_step_batch launches; 0: the members' own launches
+                                 in turn (two-launch form: SBMP_STEP=0, or a member that does not fit) */
+} sbmp_batch_info;
+/* Fails with SBMP_ERR_INVALID_ARGUMENT for count < 1 or parameters sbmp_kgmt_create rejects. */
+sbmp_status sbmp_kgmt_batch_create(const sbmp_kgmt_params* p, int count, sbmp_kgmt_batch** out);
+sbmp_status sbmp_kgmt_batch_destroy(sbmp_kgmt_batch* h);
+/* initials, goals: host arrays of count x 7 floats; seeds: count; results: count, or NULL.
+ * A NULL array or a non-finite root (x, y, theta, v) of any member fails with
+ * SBMP_ERR_INVALID_ARGUMENT before anything is launched.  plan blocks until every member has
+ * ended (goal, full tree or numIterations); a member's wallMs is taken at its own end. */
+sbmp_status sbmp_kgmt_batch_plan(sbmp_kgmt_batch* h, const float* initials, const float* goals,
+                                 const float* d_obstacles, int obstaclesCount, const uint64_t* seeds,
+                                 sbmp_plan_result* results);
+sbmp_status sbmp_kgmt_batch_begin(sbmp_kgmt_batch* h, const float* initials, const float* goals,
+                                  const float* d_obstacles, int obstaclesCount, const uint64_t* seeds);
+/* Up to `iterations` more iterations of every member, waited for; *active = members still running. */
+sbmp_status sbmp_kgmt_batch_step(sbmp_kgmt_batch* h, int iterations, int* active);
+sbmp_status sbmp_kgmt_batch_enqueue(sbmp_kgmt_batch* h, int iterations);
+sbmp_status sbmp_kgmt_batch_sync(sbmp_kgmt_batch* h);
+sbmp_status sbmp_kgmt_batch_result(sbmp_kgmt_batch* h, int member, sbmp_plan_result* result);
+/* Member i as a planner handle owned by the batch, for every read-only call above
+ * (copy_tree, copy_regions, copy_rng, iter_log, solution_path, state_hash, export_csv,
+ * path_info, kernel_stats, ...).  sbmp_kgmt_plan / begin / step / enqueue / destroy on it fail
+ * with SBMP_ERR_STATE, sbmp_kgmt_set_iteration_dump with SBMP_ERR_UNSUPPORTED. */
+sbmp_status sbmp_kgmt_batch_member(sbmp_kgmt_batch* h, int i, sbmp_kgmt** borrowed);
+sbmp_status sbmp_kgmt_batch_info(sbmp_kgmt_batch* h, sbmp_batch_info* out);
+/* The batch launches timed with profileKernels, as kernel "k_step_batch" (the members'
+ * own launches are in their sbmp_kgmt_kernel_stats). */
+sbmp_status sbmp_kgmt_batch_kernel_stat(sbmp_kgmt_batch* h, sbmp_kernel_stat* out);
+/* The packing rule alone (host-only, no device needed): members in index order into the
+ * fewest launches whose sum of groupsPerMember stays within residentGroups.
+ * launchOfMember[i] = the launch of member i, or -1 if it does not fit alone; *launches =
+ * the number of launches. */
+sbmp_status sbmp_batch_pack(const int* groupsPerMember, int count, int residentGroups, int* launchOfMember,
+                            int* launches);
+
 /* Host collectives for ranks that do not share an RCCL communicator (several
  * processes on one GPU, or a host program that already runs MPI / gloo).  Each
  * callback is collective over the nranks ranks and blocking, on host buffers, and
