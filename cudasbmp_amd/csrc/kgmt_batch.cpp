@@ -2,14 +2,22 @@
 // stream, their k_step launches of an iteration merged into k_step_batch launches
 // (kgmt_kernels.hip).
 #include <algorithm>
-#include <climits>
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
 #include "kgmt_planner.h"
 
 namespace sbmp {
+
+// f() on behalf of member i: an Error it throws names the member.
+template <typename F>
+static auto for_member(int i, F f) {
+    try {
+        return f();
+    } catch (const Error& e) {
+        throw Error(e.status, "member " + std::to_string(i) + ": " + e.what());
+    }
+}
 
 // Members in index order, each launch filled while the next member still fits: for
 // contiguous groups in a fixed order the greedy split has the fewest launches.
@@ -63,11 +71,6 @@ void BatchGroup::free_launches() {
 BatchGroup::~BatchGroup() {
     (void)hipSetDevice(p_.device);
     if (stream_) (void)hipStreamSynchronize(stream_);
-    for (auto& q : pending_) {
-        (void)hipEventDestroy(q.a);
-        (void)hipEventDestroy(q.b);
-    }
-    for (hipEvent_t e : eventPool_) (void)hipEventDestroy(e);
     for (KgmtPlanner* k : members_) delete k;
     free_launches();
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -81,13 +84,9 @@ KgmtPlanner& BatchGroup::member(int i) {
 void BatchGroup::begin(const float* initials, const float* goals, const float* d_obstacles, int nObs,
                        const uint64_t* seeds) {
     if (!initials || !goals || !seeds) throw Error(SBMP_ERR_INVALID_ARGUMENT, "initials/goals/seeds must be non-NULL");
-    if (nObs < 0 || (nObs > 0 && !d_obstacles)) throw Error(SBMP_ERR_INVALID_ARGUMENT, "bad obstacles");
     const int B = count();
-    for (int m = 0; m < B; ++m)   // D15, for every member before anything is launched
-        for (int i = 0; i < 4; ++i)
-            if (!std::isfinite(initials[7 * m + i]))
-                throw Error(SBMP_ERR_INVALID_ARGUMENT,
-                            "member " + std::to_string(m) + ": initial state (x, y, theta, v) must be finite");
+    for (int m = 0; m < B; ++m)   // every member's arguments before anything is launched
+        for_member(m, [&] { KgmtPlanner::check_begin_args(initials + 7 * m, goals + 7 * m, d_obstacles, nObs); });
     SBMP_HIP(hipSetDevice(p_.device));
     begun_ = false;
     for (int m = 0; m < B; ++m) members_[m]->begin(initials + 7 * m, goals + 7 * m, d_obstacles, nObs, seeds[m]);
@@ -171,23 +170,12 @@ void BatchGroup::begin(const float* initials, const float* goals, const float* d
     begun_ = true;
 }
 
-// The lowest iteration whose planner workgroup has run, over the members (their pinned
-// poll words): every launch (and table copy) of an earlier iteration has completed.
-int BatchGroup::min_seen() const {
-    int lo = INT_MAX;
-    for (const KgmtPlanner* k : members_) {
-        const unsigned long long v = *const_cast<const volatile unsigned long long*>(&k->poll_->word);
-        lo = std::min(lo, (int)(v >> 2));
-    }
-    return lo;
-}
-
 // The batch launches of iteration t (expand == 0: its flush pass), back to back.
 void BatchGroup::issue(int t, int expand) {
     for (Launch& l : launches_) {
         KgmtPlanner& k0 = *members_[l.first];
         launch_step_batch(k0.d_, t, expand, k0.p_.agent, k0.expandVariant_, l.dTable, l.members, l.maxGroups, stream_,
-                          expand ? timing() : KernelTiming());
+                          expand ? timer_.take(0, members_[0]->p_.profileKernels != 0) : KernelTiming());
     }
 }
 
@@ -246,24 +234,14 @@ int BatchGroup::active() {
     if (!begun_) return 0;
     flush();
     int n = 0;
-    for (int m = 0; m < count(); ++m) {
-        try {
-            if (members_[m]->active()) ++n;
-        } catch (const Error& e) {
-            throw Error(e.status, "member " + std::to_string(m) + ": " + e.what());
-        }
-    }
+    for (int m = 0; m < count(); ++m)
+        if (for_member(m, [&] { return members_[m]->active(); })) ++n;
     return n;
 }
 
-// plan(): KgmtPlanner::run_to_goal for every member at once.  kAhead iterations stay in
-// flight behind the slowest member's planner; a member has ended when its planner's word
-// says so (goal, or loop end), and its wallMs is taken once that launch has ended (a later
-// launch's planner has stored its word, or the stream is idle).  A finished member stays in
-// the later tables: its workgroups are no-ops.
+// plan(): KgmtPlanner::run_to_goal over the members, an iteration of all of them per step.
 void BatchGroup::run_plan() {
     if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
-    const int B = count();
     if (!batched_) {   // the members' own launches in turn, polled as Planner::run does
         while (true) {
             enqueue(8);
@@ -272,79 +250,14 @@ void BatchGroup::run_plan() {
         sync();
         return;
     }
-#ifndef SBMP_PLAN_AHEAD
-#define SBMP_PLAN_AHEAD 3
-#endif
-    constexpr int kAhead = SBMP_PLAN_AHEAD;
-    const int numIterations = p_.numIterations;
-    std::vector<int> endSeen(B, -1);   // the launch whose planner first reported member m's end
-    std::vector<char> fixed(B, 0);
-    int issued = members_[0]->t_next_ - 1;
-    while (true) {
-        int minSeen = INT_MAX, waiting = 0, reported = 0;
-        for (int m = 0; m < B; ++m) {
-            KgmtPlanner* k = members_[m];
-            const unsigned long long v = *const_cast<const volatile unsigned long long*>(&k->poll_->word);
-            const int seen = (int)(v >> 2);
-            minSeen = std::min(minSeen, seen);
-            if (endSeen[m] < 0 && (v & 3ull)) endSeen[m] = seen;
-            if (endSeen[m] >= 0) ++reported;
-            if (endSeen[m] >= 0 && !fixed[m]) {
-                if (seen > endSeen[m]) {
-                    k->wallMs_ = now_ms() - k->t0_;
-                    k->wallFixed_ = true;
-                    fixed[m] = 1;
-                } else {
-                    ++waiting;
-                }
-            }
-        }
-        if (waiting && hipStreamQuery(stream_) != hipErrorNotReady) {   // idle (or failed: sync() raises it)
-            for (int m = 0; m < B; ++m)
-                if (endSeen[m] >= 0 && !fixed[m]) {
-                    members_[m]->wallMs_ = now_ms() - members_[m]->t0_;
-                    members_[m]->wallFixed_ = true;
-                    fixed[m] = 1;
-                }
-            waiting = 0;
-        }
-        if (reported == B) {
-            if (!waiting) break;
-        } else if (members_[0]->t_next_ <= numIterations && issued - minSeen < kAhead) {
-            enqueue(1);
-            ++issued;
-            continue;
-        } else if (members_[0]->t_next_ > numIterations) {
-            break;   // every iteration launched: sync() ends it
-        } else {   // the stream drained (or failed) without the words this loop waits for: sync() decides
-            const hipError_t q = hipStreamQuery(stream_);
-            if (q != hipErrorNotReady && (q != hipSuccess || min_seen() < issued)) break;
-        }
-        __builtin_ia32_pause();
-    }
-    sync();
-    // a bounded in-kernel wait that gave up: raised here, whether or not a result is read
-    for (KgmtPlanner* k : members_)
-        SBMP_HIP(hipMemcpyAsync(&k->poll_->status, k->d_.status, sizeof(PlannerStatus), hipMemcpyDeviceToHost, stream_));
-    SBMP_HIP(hipStreamSynchronize(stream_));
-    for (int m = 0; m < B; ++m) {
-        if (!members_[m]->poll_->status.error) continue;
-        try {
-            throw_wait_error(members_[m]->poll_->status.error);
-        } catch (const Error& e) {
-            throw Error(e.status, "member " + std::to_string(m) + ": " + e.what());
-        }
-    }
+    KgmtPlanner::run_to_goal(members_.data(), count(), [this] { enqueue(1); }, [this] { sync(); },
+                             [](int m, int e) { for_member(m, [e] { throw_wait_error(e); }); });
 }
 
 void BatchGroup::result(int i, sbmp_plan_result* r) {
     KgmtPlanner& k = member(i);
     flush();
-    try {
-        k.result(r);
-    } catch (const Error& e) {
-        throw Error(e.status, "member " + std::to_string(i) + ": " + e.what());
-    }
+    for_member(i, [&] { k.result(r); });
 }
 
 void BatchGroup::info(sbmp_batch_info* out) const {
@@ -356,42 +269,13 @@ void BatchGroup::info(sbmp_batch_info* out) const {
     out->batched = batched_ ? 1 : 0;
 }
 
-// ---------------------------------------------------------------- profiling
-KernelTiming BatchGroup::timing() {
-    KernelTiming tm;
-    if (!members_[0]->p_.profileKernels) return tm;
-    for (hipEvent_t* e : {&tm.start, &tm.stop}) {
-        if (!eventPool_.empty()) {
-            *e = eventPool_.back();
-            eventPool_.pop_back();
-        } else {
-            SBMP_HIP(hipEventCreate(e));
-        }
-    }
-    pending_.push_back({tm.start, tm.stop});
-    return tm;
-}
-
-void BatchGroup::collect_events() {
-    for (auto& q : pending_) {
-        SBMP_HIP(hipEventSynchronize(q.b));
-        float ms = 0.0f;
-        SBMP_HIP(hipEventElapsedTime(&ms, q.a, q.b));
-        statLaunches_ += 1;
-        statMs_ += ms;
-        eventPool_.push_back(q.a);
-        eventPool_.push_back(q.b);
-    }
-    pending_.clear();
-}
-
 sbmp_kernel_stat BatchGroup::kernel_stat() {
-    collect_events();
+    timer_.collect();
     sbmp_kernel_stat s;
     memset(&s, 0, sizeof(s));
     strncpy(s.name, "k_step_batch", sizeof(s.name) - 1);
-    s.launches = statLaunches_;
-    s.totalMs = statMs_;
+    s.launches = timer_.launches(0);
+    s.totalMs = timer_.total_ms(0);
     return s;
 }
 

@@ -2332,43 +2332,65 @@ static size_t step_lds_bytes(const KgmtDev& d, int obs) {
     return b;
 }
 
-// The k_step instantiation of a plan and its dynamic LDS: what launch_step launches is
-// what step_resident_groups asked the occupancy query about.
-using StepFn = decltype(&k_step<0, kObsGlobal, false>);
+// A step kernel's instantiation for a plan and its dynamic LDS: what launch_step /
+// launch_step_batch launch is what the residency query asked about.
+template <typename Fn>
 struct StepKernel {
-    StepFn fn;
+    Fn fn;
     size_t lds;
 };
-static StepKernel step_kernel(const KgmtDev& d, int agent, int variant) {
+using StepFn = decltype(&k_step<0, kObsGlobal, false>);
+using StepBatchFn = decltype(&k_step_batch<0, kObsGlobal>);
+
+static StepKernel<StepFn> step_kernel(const KgmtDev& d, int agent, int variant) {
     return with_obs_form(d, variant, [&](auto obs) {
         const StepFn fn = (agent == 0) ? (d.sharded ? k_step<0, obs.value, true> : k_step<0, obs.value, false>)
                                        : (d.sharded ? k_step<1, obs.value, true> : k_step<1, obs.value, false>);
-        return StepKernel{fn, step_lds_bytes(d, obs.value)};
+        return StepKernel<StepFn>{fn, step_lds_bytes(d, obs.value)};
     });
 }
 
-int step_resident_groups(const KgmtDev& d, int agent, int variant, StepResidency* why) {
-    const StepKernel k = step_kernel(d, agent, variant);
+// k_step_batch for plans of d's form (unsharded)
+static StepKernel<StepBatchFn> step_batch_kernel(const KgmtDev& d, int agent, int variant) {
+    return with_obs_form(d, variant, [&](auto obs) {
+        const StepBatchFn fn = (agent == 0) ? k_step_batch<0, obs.value> : k_step_batch<1, obs.value>;
+        return StepKernel<StepBatchFn>{fn, step_lds_bytes(d, obs.value)};
+    });
+}
+
+// Workgroups of kBlock threads of fn, with lds bytes of dynamic LDS, that the current
+// device holds at once (0: the query failed).
+static int resident_groups(const void* fn, size_t lds, StepResidency* why) {
     int dev = 0, cus = 0, perCU = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (k.lds > 65536)   // LDS above 64 KB needs the opt-in (not reached by k_step's forms, kept for safety)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)k.lds);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, reinterpret_cast<const void*>(k.fn), kBlock, k.lds) !=
-        hipSuccess)
-        return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, fn, kBlock, lds) != hipSuccess) return 0;
     if (why) {
         why->perCU = perCU;
         why->cus = cus;
-        why->dynLds = (long long)k.lds;
+        why->dynLds = (long long)lds;
     }
     return perCU * cus;
 }
 
+int step_resident_groups(const KgmtDev& d, int agent, int variant, StepResidency* why) {
+    const auto k = step_kernel(d, agent, variant);
+    if (k.lds > 65536)   // LDS above 64 KB needs the opt-in (not reached by k_step's forms, kept for safety)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)k.lds);
+    return resident_groups(reinterpret_cast<const void*>(k.fn), k.lds, why);
+}
+
+int step_batch_resident_groups(const KgmtDev& d, int agent, int variant, StepResidency* why) {
+    if (d.sharded) return 0;
+    const auto k = step_batch_kernel(d, agent, variant);
+    if (k.lds > 65536) return 0;   // not reached by k_step's forms
+    return resident_groups(reinterpret_cast<const void*>(k.fn), k.lds, why);
+}
+
 void launch_step(const KgmtDev& d, int t, int expand, int agent, int variant, hipStream_t s,
                  const KernelTiming& tm) {
-    const StepKernel k = step_kernel(d, agent, variant);
+    const auto k = step_kernel(d, agent, variant);
     const bool sh = d.sharded;
     const int blocks = sh ? d.nBlocks / d.nranks : d.nBlocks;
     const dim3 grid(1 + blocks), block(kBlock);   // workgroup 0 plans, 1.. expand
@@ -2378,38 +2400,6 @@ void launch_step(const KgmtDev& d, int t, int expand, int agent, int variant, hi
     launch(k.fn, grid, block, k.lds, s, tm, d.devSelf, (int)((unsigned)t | ((unsigned)(expand != 0) << 31)),
            sh ? (d.rank | (d.nranks << 8)) : (1 << 8), cnt4, d.ctrl + (t - 1), d.rngA, d.rngB, d.gnewOut, d.status,
            tlBase, blocks, sh ? reinterpret_cast<const int*>(d.stepXr + d.xCntOff) : nullptr);
-}
-
-// The k_step_batch instantiation for plans of d's form (unsharded) and its dynamic LDS:
-// what launch_step_batch launches is what step_batch_resident_groups asked about.
-using StepBatchFn = decltype(&k_step_batch<0, kObsGlobal>);
-struct StepBatchKernel {
-    StepBatchFn fn;
-    size_t lds;
-};
-static StepBatchKernel step_batch_kernel(const KgmtDev& d, int agent, int variant) {
-    return with_obs_form(d, variant, [&](auto obs) {
-        const StepBatchFn fn = (agent == 0) ? k_step_batch<0, obs.value> : k_step_batch<1, obs.value>;
-        return StepBatchKernel{fn, step_lds_bytes(d, obs.value)};
-    });
-}
-
-int step_batch_resident_groups(const KgmtDev& d, int agent, int variant, StepResidency* why) {
-    if (d.sharded) return 0;
-    const StepBatchKernel k = step_batch_kernel(d, agent, variant);
-    int dev = 0, cus = 0, perCU = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (k.lds > 65536) return 0;   // not reached by k_step's forms
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, reinterpret_cast<const void*>(k.fn), kBlock, k.lds) !=
-        hipSuccess)
-        return 0;
-    if (why) {
-        why->perCU = perCU;
-        why->cus = cus;
-        why->dynLds = (long long)k.lds;
-    }
-    return perCU * cus;
 }
 
 void step_batch_record(const KgmtDev& d, StepBatchRec* r) {
@@ -2426,7 +2416,7 @@ void step_batch_record(const KgmtDev& d, StepBatchRec* r) {
 
 void launch_step_batch(const KgmtDev& d, int t, int expand, int agent, int variant, const StepBatchRec* table,
                        int members, int maxGroups, hipStream_t s, const KernelTiming& tm) {
-    const StepBatchKernel k = step_batch_kernel(d, agent, variant);
+    const auto k = step_batch_kernel(d, agent, variant);
     const dim3 grid(maxGroups, members), block(kBlock);   // row y: member y (workgroup 0 plans, 1.. expand)
     launch(k.fn, grid, block, k.lds, s, tm, table, (int)((unsigned)t | ((unsigned)(expand != 0) << 31)));
 }

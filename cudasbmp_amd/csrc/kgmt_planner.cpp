@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -570,11 +571,6 @@ KgmtPlanner::~KgmtPlanner() {
         (void)hipSetDevice(p_.device);
         (void)hipStreamSynchronize(stream_);
     }
-    for (auto& q : pending_) {
-        (void)hipEventDestroy(q.a);
-        (void)hipEventDestroy(q.b);
-    }
-    for (hipEvent_t e : eventPool_) (void)hipEventDestroy(e);
     for (void* ptr : allocs_) (void)hipFree(ptr);
     if (poll_) (void)hipHostFree(poll_);
     if (obs_) (void)hipFree(obs_);
@@ -584,7 +580,7 @@ KgmtPlanner::~KgmtPlanner() {
     if (stream_ && ownStream_) (void)hipStreamDestroy(stream_);
 }
 
-void KgmtPlanner::begin(const float* initial, const float* goal, const float* d_obstacles, int nObs, uint64_t seed) {
+void KgmtPlanner::check_begin_args(const float* initial, const float* goal, const float* d_obstacles, int nObs) {
     if (!initial || !goal) throw Error(SBMP_ERR_INVALID_ARGUMENT, "initial/goal must be non-NULL");
     if (nObs < 0 || (nObs > 0 && !d_obstacles)) throw Error(SBMP_ERR_INVALID_ARGUMENT, "bad obstacles");
     // D15: a non-finite root (x, y, theta, v) would only propagate NaN children; the
@@ -592,6 +588,10 @@ void KgmtPlanner::begin(const float* initial, const float* goal, const float* d_
     for (int i = 0; i < 4; ++i)
         if (!std::isfinite(initial[i]))
             throw Error(SBMP_ERR_INVALID_ARGUMENT, "initial state (x, y, theta, v) must be finite");
+}
+
+void KgmtPlanner::begin(const float* initial, const float* goal, const float* d_obstacles, int nObs, uint64_t seed) {
+    check_begin_args(initial, goal, d_obstacles, nObs);
     SBMP_HIP(hipSetDevice(p_.device));
     KgmtDev& d = d_;
     hipStream_t s = stream_;
@@ -995,62 +995,93 @@ void Planner::run(int pollEvery) {
     sync();
 }
 
-// plan(): a single k_step rank keeps kAhead iterations in flight and watches the pinned
-// word its planner workgroups store (KgmtDev::hostPoll) instead of polling with stream
-// synchronisations (run(8): a flush launch, two copies and a synchronisation every 8
-// iterations).  The planner of launch t inserts t-1's children and checks them for the
-// goal, so when its word says "goal" (or "loop ended"), the plan ends with launch t:
-// wallMs is taken when launch t has ended (the next launch's planner has stored its word:
-// a planner whose loop has ended stores it too; or the stream is idle), before the
-// launches already queued behind it (no-ops: a found goal or an ended loop stops every
-// later iteration) drain.  A planner that finds status.error set (an earlier launch's
-// bounded wait gave up) reports the loop as ended, and the error is raised after sync().
-// Time-to-first-solution is then the end of the iteration that inserts the goal node
-// (BASELINE.md), without the polls.  The result is the same as run(8)'s.
 void KgmtPlanner::run_plan() {
-    if (d_.stepMode && !d_.sharded && d_.hostPoll && dumpDir_.empty()) run_to_goal();
-    else run(8);
+    if (!(d_.stepMode && !d_.sharded && d_.hostPoll && dumpDir_.empty())) return run(8);
+    KgmtPlanner* self = this;
+    run_to_goal(&self, 1, [this] { enqueue(1); }, [this] { sync(); }, [](int, int e) { throw_wait_error(e); });
 }
 
-void KgmtPlanner::run_to_goal() {
+// plan() of single k_step ranks, one planner or the members of a BatchGroup (which advance
+// together: every launch carries the same iteration of all of them).  The host keeps kAhead
+// iterations in flight behind the slowest member's planner and watches the pinned words the
+// planner workgroups store (KgmtDev::hostPoll) instead of polling with stream
+// synchronisations (run(8): a flush launch, two copies and a synchronisation every 8
+// iterations).  The planner of launch t inserts t-1's children and checks them for the
+// goal, so when a member's word says "goal" (or "loop ended"), its plan ends with launch t:
+// its wallMs is taken when launch t has ended (a later launch's planner has stored its word:
+// a planner whose loop has ended stores it too; or the stream is idle), before the
+// launches already queued behind it (no-ops: a found goal or an ended loop stops every
+// later iteration; a finished member stays in a batch's later tables, its workgroups
+// no-ops) drain.  A planner that finds status.error set (an earlier launch's bounded wait
+// gave up) reports the loop as ended, and the error is raised after finish().
+// Time-to-first-solution is then the end of the iteration that inserts the goal node
+// (BASELINE.md), without the polls.  The result is the same as run(8)'s.
 #ifndef SBMP_PLAN_AHEAD
-#define SBMP_PLAN_AHEAD 3
+#define SBMP_PLAN_AHEAD 3   // iterations in flight (2, 3, 4 within noise; 6 slower: profiles/r05/ttfs/)
 #endif
-    constexpr int kAhead = SBMP_PLAN_AHEAD;   // iterations in flight (2, 3, 4 within noise; 6 slower: profiles/r05/ttfs/)
-    const volatile unsigned long long* w = &poll_->word;
-    int issued = t_next_ - 1;   // iterations launched
-    int goalSeen = -1;          // the launch whose planner first reported the goal (or the loop's end)
+void KgmtPlanner::run_to_goal(KgmtPlanner* const* ks, int count, const std::function<void()>& enqueueOne,
+                              const std::function<void()>& finish, const std::function<void(int, int)>& raise) {
+    constexpr int kAhead = SBMP_PLAN_AHEAD;
+    KgmtPlanner& k0 = *ks[0];   // the members share the stream, the iteration count and t_next_
+    const hipStream_t stream = k0.stream_;
+    const int numIterations = k0.p_.numIterations;
+    struct Member {
+        int endSeen = -1;     // the launch whose planner first reported the goal (or the loop's end)
+        bool fixed = false;   // its wallMs has been taken
+    };
+    std::vector<Member> st(count);
+    const auto fix_wall = [](KgmtPlanner* k, Member& m) {
+        k->wallMs_ = now_ms() - k->t0_;
+        k->wallFixed_ = true;
+        m.fixed = true;
+    };
+    int issued = k0.t_next_ - 1;   // iterations launched
     while (true) {
-        const unsigned long long v = *w;
-        const int seen = (int)(v >> 2);   // the last launch whose planner has run
-        if (goalSeen < 0 && (v & 3ull)) goalSeen = seen;
-        // launch goalSeen has ended once a later launch's planner has run (stream order), or
-        // once the stream is idle; no event per launch (their marker packets cost ~2 us each)
-        if (goalSeen >= 0) {
-            const hipError_t q = (seen > goalSeen) ? hipSuccess : hipStreamQuery(stream_);
-            if (seen > goalSeen || q != hipErrorNotReady) {
-                wallMs_ = now_ms() - t0_;
-                wallFixed_ = true;
-                break;
-            }
-        } else if (t_next_ <= p_.numIterations && issued - seen < kAhead) {
-            enqueue(1);
+        int minSeen = INT_MAX, waiting = 0, reported = 0;
+        for (int m = 0; m < count; ++m) {
+            const PollWord w = read_poll_word(&ks[m]->poll_->word);
+            minSeen = std::min(minSeen, w.seen);
+            if (st[m].endSeen < 0 && w.end) st[m].endSeen = w.seen;
+            if (st[m].endSeen < 0) continue;
+            ++reported;
+            // launch endSeen has ended once a later launch's planner has run (stream order), or
+            // once the stream is idle; no event per launch (their marker packets cost ~2 us each)
+            if (st[m].fixed) continue;
+            if (w.seen > st[m].endSeen) fix_wall(ks[m], st[m]);
+            else ++waiting;
+        }
+        if (waiting && hipStreamQuery(stream) != hipErrorNotReady) {   // idle (or failed: finish() raises it)
+            for (int m = 0; m < count; ++m)
+                if (st[m].endSeen >= 0 && !st[m].fixed) fix_wall(ks[m], st[m]);
+            waiting = 0;
+        }
+        if (reported == count) {
+            if (!waiting) break;
+        } else if (k0.t_next_ <= numIterations && issued - minSeen < kAhead) {
+            enqueueOne();
             ++issued;
             continue;
-        } else if (t_next_ > p_.numIterations) {
-            break;   // every iteration launched: sync() ends it
-        } else {   // the stream drained (or failed) without the word this loop waits for: sync() decides
-            const hipError_t q = hipStreamQuery(stream_);
-            if (q != hipErrorNotReady && (q != hipSuccess || (int)((*w) >> 2) < issued)) break;
+        } else if (k0.t_next_ > numIterations) {
+            break;   // every iteration launched: finish() ends it
+        } else {   // the stream drained (or failed) without the words this loop waits for: finish() decides
+            const hipError_t q = hipStreamQuery(stream);
+            if (q != hipErrorNotReady) {
+                int lo = INT_MAX;
+                for (int m = 0; m < count; ++m) lo = std::min(lo, read_poll_word(&ks[m]->poll_->word).seen);
+                if (q != hipSuccess || lo < issued) break;
+            }
         }
         __builtin_ia32_pause();
     }
-    sync();
+    finish();
     // a bounded in-kernel wait that gave up (its planner's word ended the loop above):
     // raised here, as run(8) raises it from active(), whether or not a result is read
-    SBMP_HIP(hipMemcpyAsync(&poll_->status, d_.status, sizeof(PlannerStatus), hipMemcpyDeviceToHost, stream_));
-    SBMP_HIP(hipStreamSynchronize(stream_));
-    if (poll_->status.error) throw_wait_error(poll_->status.error);
+    for (int m = 0; m < count; ++m)
+        SBMP_HIP(hipMemcpyAsync(&ks[m]->poll_->status, ks[m]->d_.status, sizeof(PlannerStatus), hipMemcpyDeviceToHost,
+                                stream));
+    SBMP_HIP(hipStreamSynchronize(stream));
+    for (int m = 0; m < count; ++m)
+        if (ks[m]->poll_->status.error) raise(m, ks[m]->poll_->status.error);
 }
 
 void KgmtPlanner::result(sbmp_plan_result* r) {
@@ -1374,11 +1405,17 @@ void Planner::export_csv(const std::string& dir) {
 }
 
 // ---------------------------------------------------------------- profiling
-// Events for one launch (null pair when profiling is off).  They are handed to
-// hipExtLaunchKernelGGL, which stamps them with the kernel's own start/end.
-KernelTiming KgmtPlanner::timing(int id) {
+LaunchTimer::~LaunchTimer() {
+    for (auto& q : pending_) {
+        (void)hipEventDestroy(q.a);
+        (void)hipEventDestroy(q.b);
+    }
+    for (hipEvent_t e : eventPool_) (void)hipEventDestroy(e);
+}
+
+KernelTiming LaunchTimer::take(int id, bool on) {
     KernelTiming tm;
-    if (!p_.profileKernels) return tm;
+    if (!on) return tm;
     for (hipEvent_t* e : {&tm.start, &tm.stop}) {
         if (!eventPool_.empty()) {
             *e = eventPool_.back();
@@ -1391,7 +1428,7 @@ KernelTiming KgmtPlanner::timing(int id) {
     return tm;
 }
 
-void KgmtPlanner::collect_events() {
+void LaunchTimer::collect() {
     for (auto& q : pending_) {
         SBMP_HIP(hipEventSynchronize(q.b));
         float ms = 0.0f;
@@ -1405,37 +1442,41 @@ void KgmtPlanner::collect_events() {
     pending_.clear();
 }
 
+void LaunchTimer::reset() {
+    collect();
+    for (size_t i = 0; i < launches_.size(); ++i) {
+        launches_[i] = 0;
+        totalMs_[i] = 0.0;
+        samples_[i].clear();
+    }
+}
+
 static const char* kKernelNames[] = {"k_expand", "k_finish", "k_fold_r2", "k_pack", "k_step", "k_oneshot"};
 
 std::vector<float> KgmtPlanner::kernel_samples(const std::string& name) {
-    collect_events();
+    timer_.collect();
     for (int i = 0; i < K_COUNT; ++i)
-        if (name == kKernelNames[i]) return samples_[i];
+        if (name == kKernelNames[i]) return timer_.samples(i);
     throw Error(SBMP_ERR_INVALID_ARGUMENT, "unknown kernel " + name);
 }
 
 std::vector<sbmp_kernel_stat> KgmtPlanner::kernel_stats() {
-    collect_events();
+    timer_.collect();
     const char* const* names = kKernelNames;
     std::vector<sbmp_kernel_stat> out;
     for (int i = 0; i < K_COUNT; ++i) {
         sbmp_kernel_stat s;
         memset(&s, 0, sizeof(s));
         strncpy(s.name, names[i], sizeof(s.name) - 1);
-        s.launches = launches_[i];
-        s.totalMs = totalMs_[i];
+        s.launches = timer_.launches(i);
+        s.totalMs = timer_.total_ms(i);
         out.push_back(s);
     }
     return out;
 }
 
 void KgmtPlanner::reset_kernel_stats() {
-    collect_events();
-    for (int i = 0; i < K_COUNT; ++i) {
-        launches_[i] = 0;
-        totalMs_[i] = 0.0;
-        samples_[i].clear();
-    }
+    timer_.reset();
 }
 
 }  // namespace sbmp

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -100,6 +101,44 @@ protected:
 void random_tree(int device, int kind, const float* root, int rows, int blocks, int tpb, float* samples,
                  float* kernelMs);
 
+// Times kernel launches of `ids` kinds with event pairs: the pairs are handed to
+// hipExtLaunchKernelGGL, which stamps them with the kernel's own start/end.
+class LaunchTimer {
+public:
+    explicit LaunchTimer(int ids) : launches_(ids, 0), totalMs_(ids, 0.0), samples_(ids) {}
+    ~LaunchTimer();
+    LaunchTimer(const LaunchTimer&) = delete;
+    LaunchTimer& operator=(const LaunchTimer&) = delete;
+
+    KernelTiming take(int id, bool on);   // events for one launch of kind id (a null pair when !on)
+    void collect();                       // fold the finished launches into the figures below
+    void reset();
+    long long launches(int id) const { return launches_[id]; }
+    double total_ms(int id) const { return totalMs_[id]; }
+    const std::vector<float>& samples(int id) const { return samples_[id]; }
+
+private:
+    struct Pending {
+        int id;
+        hipEvent_t a, b;
+    };
+    std::vector<Pending> pending_;
+    std::vector<hipEvent_t> eventPool_;
+    std::vector<long long> launches_;
+    std::vector<double> totalMs_;
+    std::vector<std::vector<float>> samples_;
+};
+
+// The pinned word a single rank's planner workgroups store (KgmtDev::hostPoll).
+struct PollWord {
+    int seen;   // the last launch whose planner has run
+    int end;    // nonzero: that planner found the goal, or its loop ended
+};
+inline PollWord read_poll_word(const unsigned long long* word) {
+    const unsigned long long v = *const_cast<const volatile unsigned long long*>(word);
+    return {(int)(v >> 2), (int)(v & 3ull)};
+}
+
 class KgmtPlanner : public Planner {
 public:
     // nranks > 1: rank `rank` of a sharded problem.  ex = its RCCL collectives, or
@@ -111,6 +150,8 @@ public:
     KgmtPlanner(const KgmtPlanner&) = delete;
     KgmtPlanner& operator=(const KgmtPlanner&) = delete;
 
+    // begin()'s checks of one plan's arguments (SBMP_ERR_INVALID_ARGUMENT)
+    static void check_begin_args(const float* initial, const float* goal, const float* d_obstacles, int nObs);
     void begin(const float* initial, const float* goal, const float* d_obstacles, int nObs, uint64_t seed) override;
     void enqueue(int iterations) override;
     void sync() override;
@@ -123,6 +164,13 @@ public:
     }
     void result(sbmp_plan_result* r) override;
     void run_plan() override;
+    // plan() of `count` single k_step ranks on one stream whose iterations are launched
+    // together (one planner, or a BatchGroup's members); see kgmt_planner.cpp.
+    //   enqueueOne: launches one more iteration of every member
+    //   finish:     the planner's or the group's sync()
+    //   raise:      throws member m's wait error e (throw_wait_error, with the caller's wording)
+    static void run_to_goal(KgmtPlanner* const* ks, int count, const std::function<void()>& enqueueOne,
+                            const std::function<void()>& finish, const std::function<void(int, int)>& raise);
 
     hipStream_t stream() const override { return stream_; }
     int num_slots() const override { return d_.nSlots; }
@@ -168,8 +216,7 @@ public:
 private:
     friend class BatchGroup;   // drives its members' k_step launches as one k_step_batch (kgmt_batch.cpp)
     enum KernelId { K_EXPAND = 0, K_FINISH, K_FOLD, K_PACK, K_STEP, K_XCHG, K_COUNT };
-    KernelTiming timing(int id);
-    void collect_events();
+    KernelTiming timing(int id) { return timer_.take(id, p_.profileKernels != 0); }
     void read_ctrl(std::vector<IterCtrl>& c, PlannerStatus& st);
     int last_executed(const std::vector<IterCtrl>& c) const;
     void fold_to(int tLast);
@@ -198,7 +245,6 @@ private:
         unsigned long long word;   // KgmtDev::hostPoll (single rank)
     };
     PollBuf* poll_ = nullptr;
-    void run_to_goal();                   // run_plan() for a single k_step rank
     bool wallFixed_ = false;              // wallMs_ was taken at the goal iteration's end
     bool flushed_ = true;     // k_step mode: the last enqueued iteration has been inserted
     int lastFolded_ = 0;      // iterations <= lastFolded_ are in R2Valid / R2Invalid
@@ -234,16 +280,7 @@ private:
     unsigned long long* alloc_scratch_u64();
     double wallMs_ = 0.0;
     double t0_ = 0.0;
-
-    struct Pending {
-        int id;
-        hipEvent_t a, b;
-    };
-    std::vector<Pending> pending_;
-    std::vector<hipEvent_t> eventPool_;
-    long long launches_[K_COUNT] = {0};
-    double totalMs_[K_COUNT] = {0};
-    std::vector<float> samples_[K_COUNT];
+    LaunchTimer timer_{K_COUNT};
 };
 
 // Several ranks of one sharded problem on ONE device and one stream, exchanging
@@ -339,9 +376,6 @@ private:
     void issue(int t, int expand);        // the batch launches of iteration t (or its flush pass)
     void flush();
     void stage_member(KgmtPlanner* k, int t);   // a member's own launches of iteration t
-    int min_seen() const;
-    KernelTiming timing();
-    void collect_events();
     void free_launches();
 
     sbmp_kgmt_params p_;
@@ -351,13 +385,7 @@ private:
     std::vector<int> launchOf_;
     bool begun_ = false, batched_ = false;
     int residentGroups_ = 0, groupsPerMember_ = 0, membersPerLaunch_ = 0;
-    struct Pending {
-        hipEvent_t a, b;
-    };
-    std::vector<Pending> pending_;
-    std::vector<hipEvent_t> eventPool_;
-    long long statLaunches_ = 0;
-    double statMs_ = 0.0;
+    LaunchTimer timer_{1};   // k_step_batch
 };
 
 // PlannerStatus::error -> the bounded wait that gave up (throws).

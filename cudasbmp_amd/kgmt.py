@@ -117,6 +117,23 @@ def _vec7(v) -> np.ndarray:
     return a
 
 
+def _kgmt_params(width, height, N, n, numIterations, maxTreeSize, numDisc, agentLength, goalThreshold,
+                samplesPerIteration, agent, fixGNewClear, device, profileKernels, batchRule) -> nat.KgmtParams:
+    """sbmp_kgmt_params of KGMT's (and KGMTBatch's) constructor arguments."""
+    p = nat.KgmtParams()
+    nat.call("sbmp_kgmt_default_params", ctypes.byref(p))
+    p.width, p.height, p.N, p.n = width, height, N, n
+    p.numIterations, p.maxTreeSize, p.numDisc = numIterations, maxTreeSize, numDisc
+    p.agentLength, p.goalThreshold = agentLength, goalThreshold
+    p.samplesPerIteration = samplesPerIteration
+    p.agent = AGENTS[agent]
+    p.fixGNewClear = int(bool(fixGNewClear))
+    p.device = device
+    p.profileKernels = int(bool(profileKernels))
+    p.batchRule = BATCH_RULES[batchRule]
+    return p
+
+
 class KGMT:
     """MI355X KGMT planner with the reference's constructor and plan() signature."""
 
@@ -124,17 +141,8 @@ class KGMT:
                  numDisc: int, agentLength: float, goalThreshold: float, *, samplesPerIteration: int = 0,
                  agent: str = "car", fixGNewClear: bool = False, device: int = 0, profileKernels: bool = False,
                  batchRule: str = "reference", _sharded=None, _local_group: int = 0, _host_sharded=None):
-        p = nat.KgmtParams()
-        nat.call("sbmp_kgmt_default_params", ctypes.byref(p))
-        p.width, p.height, p.N, p.n = width, height, N, n
-        p.numIterations, p.maxTreeSize, p.numDisc = numIterations, maxTreeSize, numDisc
-        p.agentLength, p.goalThreshold = agentLength, goalThreshold
-        p.samplesPerIteration = samplesPerIteration
-        p.agent = AGENTS[agent]
-        p.fixGNewClear = int(bool(fixGNewClear))
-        p.device = device
-        p.profileKernels = int(bool(profileKernels))
-        p.batchRule = BATCH_RULES[batchRule]
+        p = _kgmt_params(width, height, N, n, numIterations, maxTreeSize, numDisc, agentLength, goalThreshold,
+                        samplesPerIteration, agent, fixGNewClear, device, profileKernels, batchRule)
         self._params = p
         h = ctypes.c_void_p()
         self._coll = None
@@ -152,7 +160,12 @@ class KGMT:
             idbuf = (ctypes.c_uint8 * nat.SBMP_COMM_ID_BYTES).from_buffer_copy(bytes(uid))
             nat.call("sbmp_kgmt_create_sharded", ctypes.byref(p), idbuf, nranks, rank, ctypes.byref(h))
         self._h = h
-        # reference public fields (KGMT.cuh:34-43, 103-106)
+        self._set_reference_fields(width, height, N, n, numIterations, maxTreeSize, numDisc, agentLength,
+                                   goalThreshold)
+
+    def _set_reference_fields(self, width, height, N, n, numIterations, maxTreeSize, numDisc, agentLength,
+                              goalThreshold):
+        """The reference's public fields (KGMT.cuh:34-43, 103-106)."""
         self.width_, self.height_, self.N_, self.n_ = float(width), float(height), N, n
         self.numIterations_, self.maxTreeSize_, self.numDisc_ = numIterations, maxTreeSize, numDisc
         self.agentLength_, self.goalThreshold_ = float(agentLength), float(goalThreshold)

@@ -15,7 +15,7 @@ from typing import List, Sequence
 import numpy as np
 
 from . import _native as nat
-from .kgmt import KGMT, AGENTS, BATCH_RULES, device_ptr
+from .kgmt import KGMT, device_ptr, _kgmt_params
 
 SBMP_ERR_UNSUPPORTED = 6
 
@@ -41,13 +41,8 @@ class _Member(KGMT):
         self._h = h
         self._batch = batch   # the batch owns the planner: keep it alive
         self._coll = None
-        for k in ("width_", "height_", "N_", "n_", "numIterations_", "maxTreeSize_", "numDisc_", "agentLength_",
-                  "goalThreshold_", "R1Size_", "R2Size_"):
-            setattr(self, k, getattr(batch, k))
-        self.treeSize_ = 0
-        self.costToGoal_ = 0.0
-        self.last_result = None
-        self._obs_keepalive = None
+        self._set_reference_fields(batch.width_, batch.height_, batch.N_, batch.n_, batch.numIterations_,
+                                   batch.maxTreeSize_, batch.numDisc_, batch.agentLength_, batch.goalThreshold_)
 
     def close(self):
         self._h = ctypes.c_void_p()
@@ -65,29 +60,16 @@ class KGMTBatch:
         if _sharded is not None or _local_group or _host_sharded is not None:
             raise nat.SbmpError(SBMP_ERR_UNSUPPORTED, "KGMTBatch",
                                 "sharded and local-group planners are not supported in a batch")
-        p = nat.KgmtParams()
-        nat.call("sbmp_kgmt_default_params", ctypes.byref(p))
-        p.width, p.height, p.N, p.n = width, height, N, n
-        p.numIterations, p.maxTreeSize, p.numDisc = numIterations, maxTreeSize, numDisc
-        p.agentLength, p.goalThreshold = agentLength, goalThreshold
-        p.samplesPerIteration = samplesPerIteration
-        p.agent = AGENTS[agent]
-        p.fixGNewClear = int(bool(fixGNewClear))
-        p.device = device
-        p.profileKernels = int(bool(profileKernels))
-        p.batchRule = BATCH_RULES[batchRule]
+        p = _kgmt_params(width, height, N, n, numIterations, maxTreeSize, numDisc, agentLength, goalThreshold,
+                        samplesPerIteration, agent, fixGNewClear, device, profileKernels, batchRule)
         self._params = p
         self.count = int(count)
         h = ctypes.c_void_p()
         nat.call("sbmp_kgmt_batch_create", ctypes.byref(p), self.count, ctypes.byref(h))
         self._h = h
-        self.width_, self.height_, self.N_, self.n_ = float(width), float(height), N, n
-        self.numIterations_, self.maxTreeSize_, self.numDisc_ = numIterations, maxTreeSize, numDisc
-        self.agentLength_, self.goalThreshold_ = float(agentLength), float(goalThreshold)
-        self.R1Size_ = float(np.float32(width) / np.float32(N))
-        self.R2Size_ = float(np.float32(width) / np.float32(n * N))
+        KGMT._set_reference_fields(self, width, height, N, n, numIterations, maxTreeSize, numDisc, agentLength,
+                                   goalThreshold)
         self._members = [_Member(self, i) for i in range(self.count)]
-        self._obs_keepalive = None
 
     @classmethod
     def from_params(cls, count: int, **kw) -> "KGMTBatch":
