@@ -1251,6 +1251,12 @@ void KgmtPlanner::copy_flags(uint8_t* G, uint8_t* GNew) {
             hi = c[itr].treeSize + c[itr].A;
         }
         for (int i = lo; i < std::min(hi, M); ++i) G[i] = 1;
+        // D6: of an iteration's A rows the updateG grid writes min(A, 32 min(A, M/32)); the rest
+        // of [treeSize, treeSize + A) is counted and never written, and never enters G
+        for (int t = 1; t <= itr; ++t) {
+            const int nIns = std::min(c[t].A, 32 * std::min(c[t].A, M / 32));
+            for (int i = c[t].treeSize + nIns; i < std::min(c[t].treeSize + c[t].A, M); ++i) G[i] = 0;
+        }
     }
     if (GNew) {
         std::vector<unsigned long long> w(d_.nWords);
