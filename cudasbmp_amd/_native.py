@@ -90,7 +90,8 @@ class InsertBatchArgs(ctypes.Structure):   # sbmp_insert_batch_args
 class PathInfo(ctypes.Structure):   # sbmp_path_info
     _fields_ = [(n, ctypes.c_int) for n in ("stepForm", "obstacleForm", "residentGroups", "neededGroups", "exchange",
                                             "nranks", "rank", "commRanks", "listMirror",
-                                            "fusedExchange", "oneshotCheck", "mirrorCheck", "fusedCheck", "rowTableLds")]
+                                            "fusedExchange", "oneshotCheck", "mirrorCheck", "fusedCheck", "rowTableLds",
+                                            "rcpDivisions")]
 
 
 class BatchInfo(ctypes.Structure):   # sbmp_batch_info
@@ -119,6 +120,7 @@ EXPORTED_SYMBOLS = (
     "sbmp_kgmt_batch_create", "sbmp_kgmt_batch_destroy", "sbmp_kgmt_batch_plan", "sbmp_kgmt_batch_begin",
     "sbmp_kgmt_batch_step", "sbmp_kgmt_batch_enqueue", "sbmp_kgmt_batch_sync", "sbmp_kgmt_batch_result",
     "sbmp_kgmt_batch_member", "sbmp_kgmt_batch_info", "sbmp_kgmt_batch_kernel_stat", "sbmp_batch_pack",
+    "sbmp_division_reciprocal",
 )
 
 _lib = None
@@ -201,6 +203,7 @@ def lib():
         "sbmp_kgmt_batch_info": [vp, P(BatchInfo)],
         "sbmp_kgmt_batch_kernel_stat": [vp, P(KernelStat)],
         "sbmp_batch_pack": [vp, i, i, vp, P(i)],
+        "sbmp_division_reciprocal": [ctypes.c_float, P(ctypes.c_float)],
     }
     for name, args in sig.items():
         f = getattr(L, name)

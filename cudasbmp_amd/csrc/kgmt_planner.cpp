@@ -49,7 +49,7 @@ T* KgmtPlanner::alloc(size_t n) {
 // there (b is limited to [2^-20, 2^20], so both stay normal), so checking the 2^23
 // mantissas of one binade covers the range (tools/check_fast_division.c checks all
 // 2^32 inputs for the bench's divisors).  Cached per divisor: ~20 ms each.
-static float markstein_rcp(float b) {
+float markstein_rcp(float b) {
     static std::mutex mu;
     static std::unordered_map<uint32_t, float> cache;
     uint32_t key;
@@ -762,6 +762,8 @@ void KgmtPlanner::path_info(sbmp_path_info* out) {
     out->mirrorCheck = mirrorCheck_;
     out->fusedCheck = fusedCheck_;
     out->rowTableLds = d.c16Lds;
+    out->rcpDivisions = (d.rcpR1Size != 0.0f ? SBMP_RCP_R1SIZE : 0) | (d.rcpR2Size != 0.0f ? SBMP_RCP_R2SIZE : 0) |
+                        (d.rcpNumDisc != 0.0f ? SBMP_RCP_NUMDISC : 0) | (d.rcpAgentLength != 0.0f ? SBMP_RCP_AGENTLENGTH : 0);
 }
 
 void KgmtPlanner::build_grid(const float* d_obstacles, int nObs) {

@@ -393,4 +393,7 @@ private:
 
 double now_ms();
 
+// RN(1/b) if div_by (kgmt_device.h) was verified for the divisor b, else 0 (sbmp_division_reciprocal).
+float markstein_rcp(float b);
+
 }  // namespace sbmp

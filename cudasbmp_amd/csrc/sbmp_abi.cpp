@@ -686,4 +686,11 @@ sbmp_status sbmp_batch_pack(const int* groupsPerMember, int count, int residentG
     });
 }
 
+sbmp_status sbmp_division_reciprocal(float b, float* reciprocal) {
+    return guarded([&] {
+        REQUIRE(reciprocal, "reciprocal must be non-NULL");
+        *reciprocal = sbmp::markstein_rcp(b);
+    });
+}
+
 }  // extern "C"

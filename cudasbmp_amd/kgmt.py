@@ -97,6 +97,14 @@ def read_obstacles_csv(path: str, workspace_dim: int = 2) -> np.ndarray:
     return buf[: n.value * 2 * workspace_dim].reshape(n.value, 2 * workspace_dim).copy()
 
 
+def division_reciprocal(b: float) -> float:
+    """RN(1/b) if the kernels divide by b through the verified reciprocal, 0.0 if they take the IEEE
+    division (sbmp_division_reciprocal; host-only)."""
+    y = ctypes.c_float()
+    nat.call("sbmp_division_reciprocal", ctypes.c_float(b), ctypes.byref(y))
+    return y.value
+
+
 def device_count() -> int:
     n = ctypes.c_int()
     nat.call("sbmp_device_count", ctypes.byref(n))
@@ -336,6 +344,7 @@ class KGMT:
 
     OBSTACLE_FORMS = ("registers", "lds", "grid", "global")
     EXCHANGES = ("none", "oneshot", "collective")
+    RCP_DIVISORS = (("R1Size", 1), ("R2Size", 2), ("numDisc", 4), ("agentLength", 8))   # SBMP_RCP_*
 
     def path_info(self) -> dict:
         """The form of the hot path chosen at the last begin() (sbmp_kgmt_path_info)."""
@@ -350,7 +359,8 @@ class KGMT:
                 "oneshot_check": {0: "not run", 1: "passed", -1: "failed"}.get(pi.oneshotCheck, pi.oneshotCheck),
                 "mirror_check": {0: "not run", 1: "passed", -1: "failed"}.get(pi.mirrorCheck, pi.mirrorCheck),
                 "fused_check": {0: "not run", 1: "passed", -1: "failed"}.get(pi.fusedCheck, pi.fusedCheck),
-                "row_table_lds": bool(pi.rowTableLds)}
+                "row_table_lds": bool(pi.rowTableLds),
+                "rcp_divisions": {k: bool(pi.rcpDivisions & b) for k, b in self.RCP_DIVISORS}}
 
     def kernel_samples(self, name: str) -> np.ndarray:
         """Per-launch durations (ms) of kernel `name` since the last reset_kernel_stats()."""

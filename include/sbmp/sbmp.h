@@ -128,7 +128,15 @@ typedef struct sbmp_path_info {
     int rowTableLds;          /* sharded k_step: 1 stages the exchange's u16 block counts in LDS
                                  (row positions without a dependent load); 0 reads a row's block
                                  words (chosen when the table's LDS would cost residency) */
+    int rcpDivisions;         /* SBMP_RCP_* bits: the divisors whose divisions the kernels serve with the
+                                 host-verified reciprocal (sbmp_division_reciprocal != 0) since the last
+                                 begin(); a clear bit is an IEEE division.  The binning of a child
+                                 (bins_k) takes the reciprocal only with both R1Size and R2Size set */
 } sbmp_path_info;
+#define SBMP_RCP_R1SIZE 1
+#define SBMP_RCP_R2SIZE 2
+#define SBMP_RCP_NUMDISC 4
+#define SBMP_RCP_AGENTLENGTH 8
 
 typedef struct sbmp_kgmt sbmp_kgmt;
 
@@ -404,6 +412,11 @@ sbmp_status sbmp_kgmt_batch_kernel_stat(sbmp_kgmt_batch* h, sbmp_kernel_stat* ou
  * the number of launches. */
 sbmp_status sbmp_batch_pack(const int* groupsPerMember, int count, int residentGroups, int* launchOfMember,
                             int* launches);
+/* What the planner's constructor decides for a divisor b (host-only, no device needed):
+ * *reciprocal = RN(1/b) if the kernels' three-instruction division by b was verified to
+ * return RN(a / b) for every mantissa of a, else 0 (the kernels then divide).  The
+ * first call for a divisor checks 2^23 quotients (~20 ms); the answer is cached. */
+sbmp_status sbmp_division_reciprocal(float b, float* reciprocal);
 
 /* Host collectives for ranks that do not share an RCCL communicator (several
  * processes on one GPU, or a host program that already runs MPI / gloo).  Each
