@@ -23,6 +23,7 @@
 
 #include "kgmt_device.h"
 #include "kgmt_launch.h"
+#include "kgmt_rules.h"
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -241,12 +242,7 @@ __global__ __launch_bounds__(kBlock) void k_expand(KgmtDev d, int t) {
         bins_k(out.state.x, out.state.y, d, &r1, &r2);   // getR1 / getR2 (KGMT.cu:390-391), N = 16
         if (valid) {
             const float u = xorwow_uniform(rs);   // KGMT.cu:395
-            if (r2 >= 0) {                        // r2 >= 0 implies r1 >= 0
-                const uint32_t bit = 1u << (r2 & 31);
-                const bool r2Avail = sSnap[r2 >> 5] & bit;
-                accept = (u <= sScore[r1]) || !r2Avail;
-                if (!r2Avail) atomicOr(&sNew[r2 >> 5], bit);
-            }
+            if (r2 >= 0) accept = accept_test(u, sScore[r1], sSnap[r2 >> 5], r2, sNew);   // r2 >= 0 implies r1 >= 0
         }
         cs = out.state;
         cc = make_float4(out.a, out.steer, out.dur, __int_as_float(parent));
@@ -256,8 +252,7 @@ __global__ __launch_bounds__(kBlock) void k_expand(KgmtDev d, int t) {
         store_wt(d.rngB, slot, make_uint2(rs.v4, rs.d));
         if (r1 >= 0) atomicAdd(&sR1P[r1], valid ? 1 : 0x10000);
         if (d.r2log) {
-            d.r2log[(size_t)(t % kFoldEvery) * d.logSlots + (int)blockIdx.x * kBlock + tid] =
-                (r2 >= 0) ? (uint16_t)(r2 | (valid ? 0x8000 : 0)) : kNoKey;
+            d.r2log[(size_t)(t % kFoldEvery) * d.logSlots + (int)blockIdx.x * kBlock + tid] = r2_key(r2, valid);
         } else if (r2 >= 0) {   // more than kLogMaxR2 R2 cells: direct device atomics
             atomicAdd(valid ? &d.R2Valid[r2] : &d.R2Invalid[r2], 1);
         }
@@ -279,7 +274,7 @@ __global__ __launch_bounds__(kBlock) void k_expand(KgmtDev d, int t) {
     {   // one 64-bit atomic per touched cell, into this workgroup's replica
         unsigned long long* const rep = d.deltaOut + (size_t)(blockIdx.x % kDeltaReps) * d.nR1;
         const int v = sR1P[tid];   // nR1 == kBlock
-        if (v) atomicAdd(&rep[tid], (unsigned long long)(v & 0xffff) | ((unsigned long long)(v >> 16) << 32));
+        if (v) atomicAdd(&rep[tid], r1_delta_word(v));
     }
     for (int i = tid; i < nW; i += kBlock) {   // R2New as one byte per cell (sums merge ranks)
         uint32_t w = sNew[i];
@@ -290,12 +285,7 @@ __global__ __launch_bounds__(kBlock) void k_expand(KgmtDev d, int t) {
         }
     }
     SBMP_STAMP(6);
-    if (tl) {   // placement: XCC id << 32 | HW_ID (wave, SIMD, CU, SE fields)
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        stamp[7] = ((long long)xcc << 32) | hw;
-    }
+    if (tl) stamp[7] = placement_stamp();
     if (tl && lane == 0)
         for (int i = 0; i < kTimelineStamps; ++i) tl[i] = stamp[i];
 #undef SBMP_STAMP
@@ -399,10 +389,7 @@ __global__ __launch_bounds__(kFoldThreads) void k_fold_r2(KgmtDev d, int tFirst,
     if (ftl) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         SBMP_FSTAMP(6);
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        ftl[7] = ((long long)xcc << 32) | hw;
+        ftl[7] = placement_stamp();
     }
 #endif
 #undef SBMP_FSTAMP
@@ -512,11 +499,7 @@ __device__ void plan_iteration(const KgmtDev& d, int t, long long* st) {
     unsigned long long dl = 0ull;   // replicas: carry-free sums
 #pragma unroll
     for (int r = 0; r < kDeltaReps; ++r) dl += dv[r];
-    const int nv = (int)(dl & 0xffffffffull), ni = (int)(dl >> 32);
-    r1 += nv + ni;      // every in-grid child (KGMT.cu:392)
-    r1v += nv;          // KGMT.cu:406
-    r1i += ni;          // KGMT.cu:409
-    if (nv) r1a = 1;    // KGMT.cu:399-401
+    fold_r1_delta(dl, r1, r1v, r1i, r1a);
     // ---- R2 availability: cells seen valid while unavailable (KGMT.cu:396-402).
     // All words are decided before any is stored: a store ahead of a later word's
     // loaded data would make that use wait for the store as well (vmcnt is in order).
@@ -526,24 +509,8 @@ __device__ void plan_iteration(const KgmtDev& d, int t, long long* st) {
         const int w = tid + j * kBlock;
         nws[j] = 0u;
         if (j * kBlock < nR2w && w < nR2w) {
-            const uint32_t q[8] = {nb0[j].x, nb0[j].y, nb0[j].z, nb0[j].w, nb1[j].x, nb1[j].y, nb1[j].z, nb1[j].w};
-            uint32_t nw = 0u;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {   // nonzero bytes -> 4 bits (byte sums <= nranks never carry)
-                const uint32_t hi = (((q[k] & 0x7f7f7f7fu) + 0x7f7f7f7fu) | q[k]) & 0x80808080u;
-                nw |= ((((hi >> 7) * 0x00204081u) >> 21) & 0xfu) << (4 * k);
-            }
-            nws[j] = nw;
-            uint32_t fresh = nw & ~bits[j];
-            if (fresh && nn % 32 == 0) {   // the 32 cells of a word lie in one R1 cell
-                atomicAdd(&sCovInc[(32 * w) / nn], __popc(fresh));
-            } else {
-                while (fresh) {
-                    const int k = __builtin_ctz(fresh);
-                    fresh &= fresh - 1u;
-                    atomicAdd(&sCovInc[(32 * w + k) / nn], 1);
-                }
-            }
+            nws[j] = new_bits_from_bytes(nb0[j], nb1[j]);
+            cov_add(sCovInc, nws[j] & ~bits[j], w, nn);
         }
     }
 #pragma unroll
@@ -616,10 +583,10 @@ __device__ void plan_iteration(const KgmtDev& d, int t, long long* st) {
         for (int w = 1; w < 8; ++w) tsum = tsum + sPart[w];
         const float total = tsum;
         SBMP_FIN_STAMP(3);
-        if (own) d.R1Score[buf * d.nR1 + cell] = (r1a == 0) ? 1.0f : sc / total;
+        if (own) d.R1Score[buf * d.nR1 + cell] = normalised_score(sc, total, r1a);
     }
     SBMP_FIN_STAMP(4);
-    if (tid == 0) {
+    if (tid == 0) {   // make_ctrl (kgmt_rules.h), written out: as a call k_finish's registers changed
         IterCtrl c;
         c.run = run_t;
         c.executed = 0;
@@ -703,30 +670,16 @@ __device__ void insert_block(const KgmtDev& d, int t, int gblock, long long* st)
     for (int i = 0; i < wave; ++i) waveOff += sWaveCnt[i];
     if (word == 0ull) return;
 
-    const int m32 = d.M / 32;
-    const int grid = min(A, m32);   // updateG launch: min(|GNew|, M/32) blocks of 32 (KGMT.cu:231)
-    const int nIns = 32 * grid < A ? 32 * grid : A;
+    const InsertLimits lim = insert_limits(d.M, A);
     if (flagged) {
         const int j = waveOff + __popcll(word & ((1ull << lane) - 1ull));
         const int dst = c.treeSize + j;
-        if (j < nIns && dst < d.M) {   // D13: the reference writes past M here
-            const int parent = __float_as_int(uc.w);
-            const float cost = d.treeCtrl[parent].w + uc.z;   // getCost = duration (KGMT.cu:631-633)
-            d.treeState[dst] = us;
-            d.treeCtrl[dst] = make_float4(uc.x, uc.y, uc.z, cost);
-            d.treeParent[dst] = parent;
-            const float dx = us.x - d.goalX, dy = us.y - d.goalY;   // inGoalRegion, KGMT.cu:635-638
-            const float d2 = dx * dx + dy * dy;
-            if (__builtin_sqrtf(d2) < d.goalThreshold) atomicMin(&d.status->goalIdx, dst);
-        }
+        // (copies: handed over by reference, this kernel came out with other register numbers)
+        if (j < lim.nIns && dst < d.M) insert_row(d, dst, float4(us), float4(uc));
     }
     SBMP_FIN_STAMP(3);
-    if (lane == 0) {   // D6: only GNew[0 .. 32*grid) is cleared
-        const long long cleared = d.fixGNewClear ? (1ll << 62) : 32ll * grid;
-        const long long base = (long long)w * kWave;
-        unsigned long long nw_ = word;
-        if (base + kWave <= cleared) nw_ = 0ull;
-        else if (base < cleared) nw_ = word & ~((1ull << (cleared - base)) - 1ull);
+    if (lane == 0) {
+        const unsigned long long nw_ = d6_clear_word(word, w, d6_cleared(d.fixGNewClear, lim.grid));
         if (nw_ != word) d.gnewIn[w] = nw_;
     }
 }
@@ -800,10 +753,8 @@ __device__ void insert_blocks(const KgmtDev& d, int t, int w0, int G, long long*
     __syncthreads();
     const int A = sRed[kInsertMaxR][0] + sRed[kInsertMaxR][1] + sRed[kInsertMaxR][2] + sRed[kInsertMaxR][3];
     SBMP_FIN_STAMP(2);
-    const int m32 = d.M / 32;
-    const int grid = min(A, m32);   // updateG launch: min(|GNew|, M/32) blocks of 32 (KGMT.cu:231)
-    const int nIns = 32 * grid < A ? 32 * grid : A;
-    const long long cleared = d.fixGNewClear ? (1ll << 62) : 32ll * grid;
+    const InsertLimits lim = insert_limits(d.M, A);
+    const long long cleared = d6_cleared(d.fixGNewClear, lim.grid);
 #pragma unroll
     for (int r = 0; r < kInsertMaxR; ++r) {
         if (word[r] == 0ull) continue;   // uniform
@@ -812,23 +763,11 @@ __device__ void insert_blocks(const KgmtDev& d, int t, int w0, int G, long long*
         if (flagged[r]) {
             const int j = waveOff + __popcll(word[r] & ((1ull << lane) - 1ull));
             const int dst = c.treeSize + j;
-            if (j < nIns && dst < d.M) {   // D13: the reference writes past M here
-                const int parent = __float_as_int(uc[r].w);
-                const float cost = d.treeCtrl[parent].w + uc[r].z;   // getCost = duration (KGMT.cu:631-633)
-                d.treeState[dst] = us[r];
-                d.treeCtrl[dst] = make_float4(uc[r].x, uc[r].y, uc[r].z, cost);
-                d.treeParent[dst] = parent;
-                const float dx = us[r].x - d.goalX, dy = us[r].y - d.goalY;   // inGoalRegion, KGMT.cu:635-638
-                const float d2 = dx * dx + dy * dy;
-                if (__builtin_sqrtf(d2) < d.goalThreshold) atomicMin(&d.status->goalIdx, dst);
-            }
+            if (j < lim.nIns && dst < d.M) insert_row(d, dst, us[r], uc[r]);
         }
-        if (lane == 0) {   // D6: only GNew[0 .. 32*grid) is cleared
+        if (lane == 0) {
             const int w = gb[r] * (kBlock / kWave) + wave;
-            const long long base = (long long)w * kWave;
-            unsigned long long nw_ = word[r];
-            if (base + kWave <= cleared) nw_ = 0ull;
-            else if (base < cleared) nw_ = word[r] & ~((1ull << (cleared - base)) - 1ull);
+            const unsigned long long nw_ = d6_clear_word(word[r], w, cleared);
             if (nw_ != word[r]) d.gnewIn[w] = nw_;
         }
     }
@@ -857,9 +796,7 @@ __device__ void insert_records(const KgmtDev& d, int t, int wg, int nWG, long lo
     for (int q = 0; q < d.nranks; ++q) start[q + 1] = start[q] + d.totIn[q];
     const int A = start[d.nranks];
     SBMP_FIN_STAMP(1);
-    const int m32 = d.M / 32;
-    const int grid = min(A, m32);   // updateG launch: min(|GNew|, M/32) blocks of 32 (KGMT.cu:231)
-    const int nIns = 32 * grid < A ? 32 * grid : A;
+    const int nIns = insert_limits(d.M, A).nIns;
     for (int i = wg * kBlock + (int)threadIdx.x; i < A; i += nWG * kBlock) {
         int q = 0;
         while (q + 1 < d.nranks && i >= start[q + 1]) ++q;
@@ -869,16 +806,7 @@ __device__ void insert_records(const KgmtDev& d, int t, int wg, int nWG, long lo
         const float4 m = load_record(rec + 2);
         const int j = d.pfxIn[__float_as_int(m.x)] + __float_as_int(m.y);
         const int dst = c.treeSize + j;
-        if (j < nIns && dst < d.M) {   // D13
-            const int parent = __float_as_int(u.w);
-            const float cost = d.treeCtrl[parent].w + u.z;   // getCost = duration (KGMT.cu:631-633)
-            d.treeState[dst] = s;
-            d.treeCtrl[dst] = make_float4(u.x, u.y, u.z, cost);
-            d.treeParent[dst] = parent;
-            const float dx = s.x - d.goalX, dy = s.y - d.goalY;   // inGoalRegion, KGMT.cu:635-638
-            const float d2 = dx * dx + dy * dy;
-            if (__builtin_sqrtf(d2) < d.goalThreshold) atomicMin(&d.status->goalIdx, dst);
-        }
+        if (j < nIns && dst < d.M) insert_row(d, dst, s, u);
     }
     SBMP_FIN_STAMP(3);
 }
@@ -893,13 +821,8 @@ __device__ void owner_clear(const KgmtDev& d, int t, int lb) {
     if ((threadIdx.x & (kWave - 1)) != 0) return;
     const unsigned long long word = d.gnewOut[w];
     if (word == 0ull) return;
-    const int A = d.pfxIn[d.nBlocks];
-    const int grid = min(A, d.M / 32);
-    const long long cleared = d.fixGNewClear ? (1ll << 62) : 32ll * grid;
-    const long long base = (long long)w * kWave;
-    unsigned long long nw_ = word;
-    if (base + kWave <= cleared) nw_ = 0ull;
-    else if (base < cleared) nw_ = word & ~((1ull << (cleared - base)) - 1ull);
+    const int grid = insert_limits(d.M, d.pfxIn[d.nBlocks]).grid;
+    const unsigned long long nw_ = d6_clear_word(word, w, d6_cleared(d.fixGNewClear, grid));
     if (nw_ != word) d.gnewOut[w] = nw_;
 }
 
@@ -1535,12 +1458,7 @@ __device__ __forceinline__ void step_scan(const KgmtDev& d, int4 pk, int* sPfx, 
     *A = w0 + w1 + w2 + w3;
     const int g0 = __builtin_amdgcn_readfirstlane(sRed[1][0]), g1 = __builtin_amdgcn_readfirstlane(sRed[1][1]),
               g2 = __builtin_amdgcn_readfirstlane(sRed[1][2]), g3 = __builtin_amdgcn_readfirstlane(sRed[1][3]);
-    int jg = kNoGoalIdx;   // the lowest wave holding one has the lowest index
-    if (g3 != kNoGoalIdx) jg = w0 + w1 + w2 + g3;
-    if (g2 != kNoGoalIdx) jg = w0 + w1 + g2;
-    if (g1 != kNoGoalIdx) jg = w0 + g1;
-    if (g0 != kNoGoalIdx) jg = g0;
-    *jGoal = jg;
+    *jGoal = lowest_goal(w0, w1, w2, g0, g1, g2, g3);
     const int base = excl + (wave > 0 ? w0 : 0) + (wave > 1 ? w1 : 0) + (wave > 2 ? w2 : 0);
     if (tid * 4 + 3 <= d.nBlocks) {   // one 16-B LDS store (sPfx is 16-B aligned)
         *reinterpret_cast<int4*>(sPfx + tid * 4) = make_int4(base, base + loc[1], base + loc[2], base + loc[3]);
@@ -1757,8 +1675,9 @@ __device__ __forceinline__ StepPlan step_plan(const KgmtDev& d, int t, int expan
     q.treeSize = (t == 1) ? 1 : pc.treeSize + A;   // KGMT.cu:249
     q.gLo = (t == 1) ? 0 : pc.gLo + pc.nExp;
     const int Hprev = (t == 1) ? 0 : pc.H;
-    q.grid = min(A, d.M / 32);   // updateG launch: min(|GNew|, M/32) blocks of 32 (KGMT.cu:231)
-    q.nIns = 32 * q.grid < A ? 32 * q.grid : A;
+    const InsertLimits lim = insert_limits(d.M, A);
+    q.grid = lim.grid;
+    q.nIns = lim.nIns;
     // The lowest inserted row of t-1 inside the goal radius (D4): rows grow with j,
     // so if the lowest candidate is not inserted (D13) none is.
     q.newGoal = goalIdx;
@@ -1830,14 +1749,7 @@ __device__ __forceinline__ void step_planner(const KgmtDev& d, const ShardView& 
                 const int w = min(tid + j * kBlock, nW - 1);
                 const uint4 b0 = reinterpret_cast<const SBMP_GAS uint4*>(nbp + 32 * (size_t)w)[0];
                 const uint4 b1 = reinterpret_cast<const SBMP_GAS uint4*>(nbp + 32 * (size_t)w)[1];
-                const uint32_t qv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-                uint32_t nw = 0u;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {   // nonzero bytes -> 4 bits (sums <= nranks never carry)
-                    const uint32_t hi = (((qv[k] & 0x7f7f7f7fu) + 0x7f7f7f7fu) | qv[k]) & 0x80808080u;
-                    nw |= ((((hi >> 7) * 0x00204081u) >> 21) & 0xfu) << (4 * k);
-                }
-                newW[j] = nw;
+                newW[j] = new_bits_from_bytes(b0, b1);
             }
         }
     } else if (nW <= 2 * kBlock) {
@@ -1876,29 +1788,15 @@ __device__ __forceinline__ void step_planner(const KgmtDev& d, const ShardView& 
         }
         return;
     }
-    const int nv = (int)(dl & 0xffffffffull), ni = (int)(dl >> 32);
-    r1 += nv + ni;      // KGMT.cu:392
-    r1v += nv;          // KGMT.cu:406
-    r1i += ni;          // KGMT.cu:409
-    if (nv) r1a = 1;    // KGMT.cu:399-401
+    fold_r1_delta(dl, r1, r1v, r1i, r1a);
     uint32_t snapW[kW];
 #pragma unroll
     for (int j = 0; j < kW; ++j) {
         const int w = tid + j * kBlock;
         snapW[j] = 0u;
         if (j * kBlock < nW && w < nW) {
-            const uint32_t fresh = newW[j] & ~availW[j];
             snapW[j] = availW[j] | newW[j];   // R2Avail of t = the snapshot (D2)
-            if (fresh && nn % 32 == 0) {
-                atomicAdd(&sCovInc[(32 * w) / nn], __popc(fresh));
-            } else {
-                uint32_t f = fresh;
-                while (f) {
-                    const int b = __builtin_ctz(f);
-                    f &= f - 1u;
-                    atomicAdd(&sCovInc[(32 * w + b) / nn], 1);
-                }
-            }
+            cov_add(sCovInc, newW[j] & ~availW[j], w, nn);
         }
     }
     __syncthreads();
@@ -1926,7 +1824,7 @@ __device__ __forceinline__ void step_planner(const KgmtDev& d, const ShardView& 
         float total = sPart[0];
 #pragma unroll
         for (int w = 1; w < 8; ++w) total = total + sPart[w];
-        scv = (r1a == 0) ? 1.0f : sc / total;
+        scv = normalised_score(sc, total, r1a);
     }
     // publish first (tagged 8-B words, written through)
     SBMP_GAS unsigned long long* const pub = G(d.stepPub) + (size_t)cp * (d.nR1 + nW);
@@ -1968,20 +1866,7 @@ __device__ __forceinline__ void step_planner(const KgmtDev& d, const ShardView& 
         for (int i = tid; i < kNewReps * nW; i += kBlock) store_wt(zn, i, 0);
     }
     if (tid == 0) {
-        IterCtrl c;
-        c.run = q.runT;
-        c.executed = q.executes ? 1 : 0;
-        c.treeSize = q.treeSize;
-        c.gLo = q.gLo;
-        c.nG = q.nG;
-        c.k = q.k;
-        c.nExp = q.nExp;
-        c.S = q.S;
-        c.H = q.H;
-        c.A = 0;
-        c.scoreBuf = cp;
-        for (int i = 0; i < 5; ++i) c.pad[i] = 0;
-        st_ctrl(d.ctrl, t, c);
+        st_ctrl(d.ctrl, t, make_ctrl(q.runT, q.executes ? 1 : 0, q.treeSize, q.gLo, q.nG, q.k, q.nExp, q.S, q.H, cp));
         if (t > 1) store_wt(reinterpret_cast<int*>(d.ctrl + (t - 1)), 9, A);   // .A
         if (q.newGoal != goalIdx) store_wt(reinterpret_cast<int*>(d.status), 0, q.newGoal);   // .goalIdx
         if (d.hostPoll)   // the host's plan loop: this launch planned t (a vector store over PCIe)
@@ -2009,11 +1894,6 @@ __device__ __forceinline__ void step_planner(const KgmtDev& d, const ShardView& 
                 return list_entry<SH>(d, pp, lo, j - sPfx[lo]);
             }
         };
-        auto put = [&](int j, float4 s4, float4 u4, float c) {   // row tsPrev + j, written through
-            store_wt(d.treeState + q.tsPrev, j, s4);
-            store_wt(d.treeCtrl + q.tsPrev, j, make_float4(u4.x, u4.y, u4.z, c));   // cost = parent's + duration (KGMT.cu:631-633)
-            store_wt(d.treeParent + q.tsPrev, j, __float_as_int(u4.w));
-        };
         for (int j0 = tid; j0 < n; j0 += 2 * kBlock) {   // two rows per thread per round, loads first
             const int j1 = j0 + kBlock;
             const SBMP_GAS float4* e0 = entry(j0);
@@ -2021,8 +1901,8 @@ __device__ __forceinline__ void step_planner(const KgmtDev& d, const ShardView& 
             const float4 s0 = list_load<SH>(d, e0), u0 = list_load<SH>(d, e0 + 1), s1 = list_load<SH>(d, e1),
                          u1 = list_load<SH>(d, e1 + 1);
             const float c0 = list_load<SH>(d, e0 + 2).x, c1 = list_load<SH>(d, e1 + 2).x;
-            put(j0, s0, u0, c0);
-            if (j1 < n) put(j1, s1, u1, c1);
+            put_row(d, q.tsPrev, j0, s0, u0, c0);
+            if (j1 < n) put_row(d, q.tsPrev, j1, s1, u1, c1);
         }
     }
 }

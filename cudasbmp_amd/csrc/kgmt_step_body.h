@@ -175,15 +175,13 @@
     auto body = [&]() __attribute__((always_inline)) {
     if (!q.ranPrev) return;
 
-    // ---- D6 clear of this block's words of t-1 (KGMT.cu:231,556)
-    const long long cleared = d.fixGNewClear ? (1ll << 62) : 32ll * q.grid;
+    // ---- D6 clear of this block's words of t-1
+    const long long cleared = d6_cleared(d.fixGNewClear, q.grid);
     unsigned long long word = oldWord;
     if (d.fixGNewClear) {   // the complete clear: every word (uniform branch)
         word = 0ull;
     } else if (lane == 0) {
-        const long long wbase = (long long)(slot >> 6) * kWave;
-        if (wbase + kWave <= cleared) word = 0ull;
-        else if (wbase < cleared) word = oldWord & ~((1ull << (cleared - wbase)) - 1ull);
+        word = d6_clear_word(oldWord, slot >> 6, cleared);
     }
     const bool doExpand = q.executes && gb * kBlock < q.H;
     // ---- insert t-1: this block's flagged children (rows treeSize(t-1) + prefix +
@@ -199,11 +197,7 @@
                 const float4 s4 = list_load<SH>(d, e);
                 const float4 u4 = list_load<SH>(d, e + 1);
                 const float4 m4 = list_load<SH>(d, e + 2);
-                // written through (fewer dirty lines at the boundary); the V# based at row tsPrev keeps
-                // the byte offset j * 16 far below 2^31 whatever M is
-                store_wt(d.treeState + q.tsPrev, j, s4);
-                store_wt(d.treeCtrl + q.tsPrev, j, make_float4(u4.x, u4.y, u4.z, m4.x));   // cost = parent's + duration (KGMT.cu:631-633)
-                store_wt(d.treeParent + q.tsPrev, j, __float_as_int(u4.w));
+                put_row(d, q.tsPrev, j, s4, u4, m4.x);
             }
         }
     };
@@ -222,9 +216,7 @@
                         const float4 s4 = list_load<SH>(d, e);
                         const float4 u4 = list_load<SH>(d, e + 1);
                         const float4 m4 = list_load<SH>(d, e + 2);
-                        store_wt(d.treeState + q.tsPrev, j, s4);
-                        store_wt(d.treeCtrl + q.tsPrev, j, make_float4(u4.x, u4.y, u4.z, m4.x));
-                        store_wt(d.treeParent + q.tsPrev, j, __float_as_int(u4.w));
+                        put_row(d, q.tsPrev, j, s4, u4, m4.x);
                     }
                 }
             } else {
@@ -423,8 +415,7 @@
         store_wt(d.rngB, slot, make_uint2(rs.v4, rs.d));
         if (q1 >= 0) atomicAdd(&sR1P[q1], valid ? 1 : 0x10000);
         if (d.r2log) {
-            store_wt(d.r2log, (t % kFoldEvery) * d.logSlots + b * kBlock + tid,
-                     (q2 >= 0) ? (uint16_t)(q2 | (valid ? 0x8000 : 0)) : kNoKey);
+            store_wt(d.r2log, (t % kFoldEvery) * d.logSlots + b * kBlock + tid, r2_key(q2, valid));
         } else if (q2 >= 0) {
             __hip_atomic_fetch_add(G(valid ? d.R2Valid : d.R2Invalid) + q2, 1, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
@@ -453,7 +444,7 @@
         }
     }
     bool accept = false;
-    if (look) {
+    if (look) {   // accept_test (kgmt_rules.h), written out: as a call k_step's code changed
         const uint32_t bit = 1u << (q2 & 31);
         const bool r2Avail = (uint32_t)aw & bit;
         accept = (u <= __uint_as_float((uint32_t)sw)) || !r2Avail;
@@ -477,7 +468,8 @@
     }
     bool inGoal = false;
     if (flagged && d.goalThreshold > 0.0f) {   // sqrtf(.) < r is false for every r <= 0 (and NaN)
-        const float dx = cs.x - d.goalX, dy = cs.y - d.goalY;   // inGoalRegion, KGMT.cu:635-638
+        // in_goal (kgmt_rules.h), written out: as a call k_step's code changed
+        const float dx = cs.x - d.goalX, dy = cs.y - d.goalY;
         inGoal = __builtin_sqrtf(dx * dx + dy * dy) < d.goalThreshold;
     }
     // index among the wave's flagged slots; the first goal child is the wave's lowest
@@ -536,8 +528,7 @@
             (SH ? G(d.stepXs[cp]) : G(d.stepDelta) + (size_t)(t % 3) * kDeltaReps * d.nR1) + (size_t)(b % kDeltaReps) * d.nR1;
         const int v = sR1P[tid];   // nR1 == kBlock
         if (v)
-            __hip_atomic_fetch_add(rep + tid, (unsigned long long)(v & 0xffff) | ((unsigned long long)(v >> 16) << 32),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(rep + tid, r1_delta_word(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if constexpr (SH) {   // R2New as bytes of the exchange (a sum over ranks), one store per cell the block saw
         SBMP_GAS uint8_t* const nb = reinterpret_cast<SBMP_GAS uint8_t*>(G(d.stepXs[cp]) + d.xNewOff);
@@ -565,11 +556,7 @@
     }
     if (tid == 0) {   // the block's flagged count and its lowest goal child (in-block index)
         const int g0 = sWaveGoal[0], g1 = sWaveGoal[1], g2 = sWaveGoal[2], g3 = sWaveGoal[3];
-        int gmin = kNoGoalIdx;
-        if (g3 != kNoGoalIdx) gmin = c0 + c1 + c2 + g3;
-        if (g2 != kNoGoalIdx) gmin = c0 + c1 + g2;
-        if (g1 != kNoGoalIdx) gmin = c0 + g1;
-        if (g0 != kNoGoalIdx) gmin = g0;
+        const int gmin = lowest_goal(c0, c1, c2, g0, g1, g2, g3);
         const int cw = (c0 + c1 + c2 + c3) | ((gmin == kNoGoalIdx ? 0 : gmin + 1) << 16);
         if constexpr (SH) {   // the block word, and this rank's part of row b (the exchange sums the row); sc1
             __hip_atomic_store(reinterpret_cast<SBMP_GAS int*>(G(d.stepXs[cp]) + d.xCntOff) + gb, cw, __ATOMIC_RELAXED,
@@ -583,12 +570,7 @@
         else store_wt(d.stepCnt, cp * kMaxStepBlocks + b, cw);
     }
     SBMP_STAMP(6);
-    if (tl) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        stamp[7] = ((long long)xcc << 32) | hw;
-    }
+    if (tl) stamp[7] = placement_stamp();
     if (tl && lane == 0)
         for (int i = 0; i < kTimelineStamps; ++i) G(tl)[i] = stamp[i];
     };
