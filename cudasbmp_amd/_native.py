@@ -99,6 +99,15 @@ class BatchInfo(ctypes.Structure):   # sbmp_batch_info
                                             "launchesPerIteration", "batched")]
 
 
+class GoalQuery(ctypes.Structure):   # sbmp_goal_query
+    _fields_ = [("x", ctypes.c_float), ("y", ctypes.c_float), ("radius", ctypes.c_float)]
+
+
+class GoalAnswer(ctypes.Structure):   # sbmp_goal_answer
+    _fields_ = [("count", ctypes.c_int), ("firstRow", ctypes.c_int), ("bestRow", ctypes.c_int),
+                ("bestCost", ctypes.c_float), ("nearestRow", ctypes.c_int), ("nearestDistance", ctypes.c_float)]
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", ctypes.c_longlong), ("totalMs", ctypes.c_double)]
 
@@ -121,6 +130,7 @@ EXPORTED_SYMBOLS = (
     "sbmp_kgmt_batch_step", "sbmp_kgmt_batch_enqueue", "sbmp_kgmt_batch_sync", "sbmp_kgmt_batch_result",
     "sbmp_kgmt_batch_member", "sbmp_kgmt_batch_info", "sbmp_kgmt_batch_kernel_stat", "sbmp_batch_pack",
     "sbmp_division_reciprocal",
+    "sbmp_kgmt_query_goals", "sbmp_tree_query_batch", "sbmp_tree_query_batch_host", "sbmp_goal_radius_threshold",
 )
 
 _lib = None
@@ -204,6 +214,10 @@ def lib():
         "sbmp_kgmt_batch_kernel_stat": [vp, P(KernelStat)],
         "sbmp_batch_pack": [vp, i, i, vp, P(i)],
         "sbmp_division_reciprocal": [ctypes.c_float, P(ctypes.c_float)],
+        "sbmp_kgmt_query_goals": [vp, vp, i, vp],
+        "sbmp_tree_query_batch": [vp, vp, ctypes.c_longlong, vp, i, vp, vp],
+        "sbmp_tree_query_batch_host": [vp, vp, ctypes.c_longlong, vp, i, vp],
+        "sbmp_goal_radius_threshold": [ctypes.c_float, P(ctypes.c_float)],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -116,6 +116,20 @@ void launch_export_tree(const KgmtDev& d, float* samples, float* costs, hipStrea
 void launch_state_hash(const KgmtDev& d, int rows, int tp, int iters, unsigned long long* out, hipStream_t s);
 void launch_export_unexplored(const KgmtDev& d, float* samples, int* uParent, hipStream_t s);
 
+// tree_query.hip — k_tree_query: `count` goals (x, y, t: include/sbmp/tree_query.h's threshold
+// form) against rows [0, rows) of state (x, y, -, -) / ctrl (-, -, -, cost).  acc[count] is
+// device memory: the launch initialises it on s, then one pass over the rows per tile of up
+// to kQueryTile goals folds the rows into it; the host turns the keys into the answers.
+struct QueryAcc {
+    unsigned long long best;      // goal_key(cost, row) of the best inside row, kNoGoalKey if none
+    unsigned long long nearest;   // goal_key(d2, row) of the nearest row
+    unsigned count;               // rows inside
+    unsigned first;               // lowest row inside, ~0u if none
+};
+constexpr int kQueryTile = 16;
+void launch_tree_query(const float4* state, const float4* ctrl, long long rows, const float* goalsXYT, int count,
+                       QueryAcc* acc, hipStream_t s);
+
 // xorwow_jump.cpp: cuRAND seeding and the subsequence jump matrices.
 Xorwow curand_seed_state(uint64_t seed);
 // J[b] = A^(2^(67+b)), b < nbits, each 160 columns x 5 words, concatenated.

@@ -1166,6 +1166,19 @@ unsigned long long KgmtPlanner::state_hash() {
     return h;
 }
 
+// Goal queries over the rows copy_tree exports (k_tree_query, tree_query.hip): on the
+// planner's stream behind everything enqueued, reading treeState / treeCtrl only.
+void KgmtPlanner::query_goals(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) {
+    tree_query_check_goals(goals, count, out);
+    if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
+    if (count == 0) return;
+    sbmp_plan_result r;
+    result(&r);   // syncs (the flush pass has inserted the last iteration)
+    const int rows = std::min(std::max(r.treeSize, 1), d_.M);
+    tree_query_device(reinterpret_cast<const float*>(d_.treeState), reinterpret_cast<const float*>(d_.treeCtrl), rows,
+                      goals, count, out, stream_);
+}
+
 unsigned long long* KgmtPlanner::alloc_scratch_u64() {
     if (!scratch_) scratch_ = alloc<unsigned long long>(8);
     return scratch_;

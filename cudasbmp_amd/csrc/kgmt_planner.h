@@ -83,6 +83,9 @@ public:
     // Digest of the replicated state (tree rows, region tables, control blocks): the same on
     // every rank of a sharded run (k_state_hash).
     virtual unsigned long long state_hash() = 0;
+    // out[i] answers goals[i] over the rows copy_tree exports, [0, min(treeSize, M)), after
+    // everything enqueued has finished (k_tree_query; reads the tree only).
+    virtual void query_goals(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) = 0;
     void export_csv(const std::string& dir);
 
     virtual std::vector<sbmp_kernel_stat> kernel_stats() = 0;
@@ -100,6 +103,15 @@ protected:
 // of 7 floats into host memory.
 void random_tree(int device, int kind, const float* root, int rows, int blocks, int tpb, float* samples,
                  float* kernelMs);
+
+// Goal queries (tree_query.hip; include/sbmp/tree_query.h): the argument checks of every
+// entry point, k_tree_query over device rows on `stream` (waits for the result), and the
+// literal rule over host rows.
+void tree_query_check_goals(const sbmp_goal_query* goals, int count, const sbmp_goal_answer* out);
+void tree_query_device(const float* d_state, const float* d_ctrl, long long rows, const sbmp_goal_query* goals,
+                       int count, sbmp_goal_answer* out, hipStream_t stream);
+void tree_query_host(const float* state, const float* ctrl, long long rows, const sbmp_goal_query* goals, int count,
+                     sbmp_goal_answer* out);
 
 // Times kernel launches of `ids` kinds with event pairs: the pairs are handed to
 // hipExtLaunchKernelGGL, which stamps them with the kernel's own start/end.
@@ -185,6 +197,7 @@ public:
     std::vector<sbmp_iter_record> iter_log() override;
     int solution_path(int node, int* rows, float* samples, float* costs, int capacity) override;
     unsigned long long state_hash() override;
+    void query_goals(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) override;
 
     std::vector<sbmp_kernel_stat> kernel_stats() override;
     void path_info(sbmp_path_info* out) override;
@@ -322,6 +335,10 @@ public:
         return r0().solution_path(node, rows, samples, costs, capacity);   // every rank holds the whole tree
     }
     unsigned long long state_hash() override;   // every rank's digest; throws if they differ
+    void query_goals(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) override {
+        sync();
+        r0().query_goals(goals, count, out);   // every rank holds the whole tree
+    }
 
     std::vector<sbmp_kernel_stat> kernel_stats() override { return r0().kernel_stats(); }
     void path_info(sbmp_path_info* out) override { r0().path_info(out); }

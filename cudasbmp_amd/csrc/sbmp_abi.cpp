@@ -10,6 +10,7 @@
 #include "kgmt_planner.h"
 #include "obstacle_grid.h"
 #include "sbmp/sbmp.h"
+#include "sbmp/tree_query.h"
 
 using sbmp::Error;
 using sbmp::KgmtPlanner;
@@ -189,6 +190,24 @@ sbmp_status sbmp_expand_batch_host(const sbmp_expand_batch_args* args) {
 
 sbmp_status sbmp_insert_batch(const sbmp_insert_batch_args* args, void* stream) {
     return guarded([&] { sbmp::insert_batch(args, stream); });
+}
+
+sbmp_status sbmp_tree_query_batch(const float* d_state, const float* d_ctrl, long long rows,
+                                  const sbmp_goal_query* goals, int count, sbmp_goal_answer* out, void* stream) {
+    return guarded(
+        [&] { sbmp::tree_query_device(d_state, d_ctrl, rows, goals, count, out, static_cast<hipStream_t>(stream)); });
+}
+
+sbmp_status sbmp_tree_query_batch_host(const float* state, const float* ctrl, long long rows,
+                                       const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) {
+    return guarded([&] { sbmp::tree_query_host(state, ctrl, rows, goals, count, out); });
+}
+
+sbmp_status sbmp_goal_radius_threshold(float r, float* t) {
+    return guarded([&] {
+        REQUIRE(t, "t must be non-NULL");
+        *t = sbmp::goal_radius_threshold(r);
+    });
 }
 
 sbmp_status sbmp_comm_get_unique_id(uint8_t id[SBMP_COMM_ID_BYTES]) {
@@ -372,6 +391,13 @@ sbmp_status sbmp_kgmt_solution_path(sbmp_kgmt* h, int node, int* rows, float* sa
         if (!rows && !samples && !costs) return;
         REQUIRE(capacity >= len, "capacity smaller than the path length");
         P.solution_path(node, rows, samples, costs, capacity);
+    });
+}
+
+sbmp_status sbmp_kgmt_query_goals(sbmp_kgmt* h, const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) {
+    return guarded([&] {
+        PLANNER(h);
+        P.query_goals(goals, count, out);
     });
 }
 

@@ -279,6 +279,18 @@ class KGMT:
                      s.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n))
         return rows, s, c
 
+    def query_goals(self, goals, radius=None) -> dict:
+        """Goal discs against the tree as it stands (sbmp_kgmt_query_goals; one k_tree_query pass
+        per 16 goals): goals is (Q, 2) with one radius for all, or (Q, 3) rows of (x, y, radius).
+        Returns (Q,) arrays count, firstRow, bestRow, bestCost, nearestRow, nearestDistance over
+        the rows tree() exports; the plan goes on unchanged."""
+        from .tree_query import ANSWER_DTYPE, answers_dict, goal_array
+        g = goal_array(goals, radius)
+        out = np.zeros(max(1, len(g)), dtype=ANSWER_DTYPE)
+        nat.call("sbmp_kgmt_query_goals", self._h, g.ctypes.data_as(ctypes.c_void_p), len(g),
+                 out.ctypes.data_as(ctypes.c_void_p))
+        return answers_dict(out[: len(g)])
+
     def unexplored(self):
         M = self.M
         s = np.zeros((M, 7), dtype=np.float32)

@@ -115,6 +115,14 @@ public:
         samples.assign(7 * (size_t)n, 0.0f);
         if (n) SBMP_CHECK(sbmp_kgmt_solution_path(h_, -1, rows.data(), samples.data(), nullptr, n, &n));
     }
+    // Goal discs against the tree as it stands (sbmp_kgmt_query_goals; sbmp/tree_query.h): per
+    // goal the rows inside, the lowest of them, the cheapest of them and the nearest row.
+    // After plan(), or between steps through handle(); the plan goes on unchanged.
+    std::vector<sbmp_goal_answer> queryGoals(const std::vector<sbmp_goal_query>& goals) const {
+        std::vector<sbmp_goal_answer> out(goals.size());
+        SBMP_CHECK(sbmp_kgmt_query_goals(h_, goals.data(), (int)goals.size(), out.data()));
+        return out;
+    }
     sbmp_kgmt* handle() const { return h_; }
 
     // Public fields of KGMT.cuh:33-43 that carry meaning outside the class.

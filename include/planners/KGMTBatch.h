@@ -92,6 +92,12 @@ public:
         samples.assign(7 * (size_t)n, 0.0f);
         if (n) SBMP_CHECK(sbmp_kgmt_solution_path(m, -1, rows.data(), samples.data(), nullptr, n, &n));
     }
+    // Goal discs against member i's tree (KGMT::queryGoals).
+    std::vector<sbmp_goal_answer> queryGoals(int i, const std::vector<sbmp_goal_query>& goals) const {
+        std::vector<sbmp_goal_answer> out(goals.size());
+        SBMP_CHECK(sbmp_kgmt_query_goals(member(i), goals.data(), (int)goals.size(), out.data()));
+        return out;
+    }
     sbmp_kgmt_batch* handle() const { return h_; }
 
 private:

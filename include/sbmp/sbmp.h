@@ -227,6 +227,31 @@ sbmp_status sbmp_kgmt_set_iteration_dump(sbmp_kgmt* h, const char* dir);
 sbmp_status sbmp_kgmt_solution_path(sbmp_kgmt* h, int node, int* rows, float* samples, float* costs, int capacity,
                                     int* length);
 
+/* Goal queries against the tree as it stands (include/sbmp/tree_query.h states the rule;
+ * no reference counterpart: the reference asks its tree one question, KGMT.cu:635-638).
+ * A row (x, y) is inside goal (x, y, radius) iff sqrtf(dx * dx + dy * dy) < radius, the
+ * planner's own goal test (D18): never for radius <= 0 or NaN; radius = +inf takes every row. */
+typedef struct sbmp_goal_query {
+    float x, y, radius;
+} sbmp_goal_query;
+typedef struct sbmp_goal_answer {
+    int count;                /* rows inside */
+    int firstRow;             /* lowest row inside, -1 if none */
+    int bestRow;              /* the inside row of lowest cost (lowest row on ties), -1 if none */
+    float bestCost;           /* its cost, 0 if none */
+    int nearestRow;           /* the row of lowest squared distance over all rows (lowest row on ties) */
+    float nearestDistance;    /* sqrtf of that squared distance */
+} sbmp_goal_answer;
+/* out[i] answers goals[i] over the rows [0, min(treeSize, maxTreeSize)) after everything
+ * enqueued has finished: exactly the rows sbmp_kgmt_copy_tree exports, the root included
+ * (firstRow equals the plan's goalIndex whenever the root lies outside the disc).  One pass
+ * of k_tree_query over the tree per 16 goals, on the planner's stream; it only reads the
+ * planner's state, so it may be called after plan() and between step() / enqueue() calls
+ * and does not change what the plan goes on to compute.  Also valid on a batch member.
+ * Before the first begin(): SBMP_ERR_STATE.  goals or out NULL with count > 0, count < 0,
+ * or a goal with a non-finite x or y: SBMP_ERR_INVALID_ARGUMENT.  count == 0 is a no-op. */
+sbmp_status sbmp_kgmt_query_goals(sbmp_kgmt* h, const sbmp_goal_query* goals, int count, sbmp_goal_answer* out);
+
 sbmp_status sbmp_kgmt_kernel_stats(sbmp_kgmt* h, sbmp_kernel_stat* out, int capacity, int* count);
 /* The form of the hot path chosen at the last begin() (sbmp_path_info). */
 sbmp_status sbmp_kgmt_path_info(sbmp_kgmt* h, sbmp_path_info* out);
@@ -330,6 +355,23 @@ typedef struct sbmp_insert_batch_args {
 } sbmp_insert_batch_args;
 sbmp_status sbmp_insert_batch(const sbmp_insert_batch_args* args, void* stream);
 
+/* sbmp_tree_query_batch: the goal query of sbmp_kgmt_query_goals (k_tree_query) over caller
+ * rows: d_state and d_ctrl are device arrays of rows x 4 floats, (x, y, -, -) and
+ * (-, -, -, cost), the planner's tree layout; 1 <= rows < 2^31.  goals and out are host
+ * arrays of count entries.  Waits for the result.  Errors as sbmp_kgmt_query_goals.
+ * sbmp_tree_query_batch_host answers the same over host rows with a plain loop that applies
+ * the literal sqrtf(d2) < radius rule to every row (the kernel compares d2 with a
+ * threshold): a second statement of the rule, and it needs no device. */
+sbmp_status sbmp_tree_query_batch(const float* d_state, const float* d_ctrl, long long rows,
+                                  const sbmp_goal_query* goals, int count, sbmp_goal_answer* out,
+                                  void* stream /* hipStream_t; NULL: default */);
+sbmp_status sbmp_tree_query_batch_host(const float* state, const float* ctrl, long long rows,
+                                       const sbmp_goal_query* goals, int count, sbmp_goal_answer* out);
+/* The threshold the kernel compares d2 with (host-only, no device needed): *t = the largest
+ * float d2 with sqrtf(d2) < r, found by bisecting the float bit patterns with that rule;
+ * FLT_MAX for r = +inf; -1 (no d2 is inside) for r <= 0 and for NaN. */
+sbmp_status sbmp_goal_radius_threshold(float r, float* t);
+
 /* Device memory helpers replacing demos/main.cu:60-61,64 (cudaMalloc/cudaMemcpy/cudaFree). */
 sbmp_status sbmp_device_upload_f32(const float* host, size_t count, float** d_out);
 sbmp_status sbmp_device_free(void* d_ptr);
@@ -398,8 +440,8 @@ sbmp_status sbmp_kgmt_batch_enqueue(sbmp_kgmt_batch* h, int iterations);
 sbmp_status sbmp_kgmt_batch_sync(sbmp_kgmt_batch* h);
 sbmp_status sbmp_kgmt_batch_result(sbmp_kgmt_batch* h, int member, sbmp_plan_result* result);
 /* Member i as a planner handle owned by the batch, for every read-only call above
- * (copy_tree, copy_regions, copy_rng, iter_log, solution_path, state_hash, export_csv,
- * path_info, kernel_stats, ...).  sbmp_kgmt_plan / begin / step / enqueue / destroy on it fail
+ * (copy_tree, copy_regions, copy_rng, iter_log, solution_path, query_goals, state_hash,
+ * export_csv, path_info, kernel_stats, ...).  sbmp_kgmt_plan / begin / step / enqueue / destroy on it fail
  * with SBMP_ERR_STATE, sbmp_kgmt_set_iteration_dump with SBMP_ERR_UNSUPPORTED. */
 sbmp_status sbmp_kgmt_batch_member(sbmp_kgmt_batch* h, int i, sbmp_kgmt** borrowed);
 sbmp_status sbmp_kgmt_batch_info(sbmp_kgmt_batch* h, sbmp_batch_info* out);
