@@ -108,6 +108,20 @@ class GoalAnswer(ctypes.Structure):   # sbmp_goal_answer
                 ("bestCost", ctypes.c_float), ("nearestRow", ctypes.c_int), ("nearestDistance", ctypes.c_float)]
 
 
+class TreeRecheck(ctypes.Structure):   # sbmp_tree_recheck
+    _fields_ = [(n, ctypes.c_int) for n in ("rows", "alive", "blocked", "stale", "orphan", "cut", "firstDead")]
+
+
+class TreeRecheckArgs(ctypes.Structure):   # sbmp_tree_recheck_args
+    _fields_ = [("state", ctypes.c_void_p), ("ctrl", ctypes.c_void_p), ("parent", ctypes.c_void_p),
+                ("rows", ctypes.c_int), ("depthBound", ctypes.c_int), ("agent", ctypes.c_int),
+                ("numDisc", ctypes.c_int), ("agentLength", ctypes.c_float), ("width", ctypes.c_float),
+                ("height", ctypes.c_float), ("obstacles", ctypes.c_void_p), ("obstaclesCount", ctypes.c_int)]
+
+
+SBMP_ROW_FREE, SBMP_ROW_ORPHAN, SBMP_ROW_BLOCKED, SBMP_ROW_STALE, SBMP_ROW_CUT = 0, 1, 2, 3, 0x80
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", ctypes.c_longlong), ("totalMs", ctypes.c_double)]
 
@@ -131,6 +145,7 @@ EXPORTED_SYMBOLS = (
     "sbmp_kgmt_batch_member", "sbmp_kgmt_batch_info", "sbmp_kgmt_batch_kernel_stat", "sbmp_batch_pack",
     "sbmp_division_reciprocal",
     "sbmp_kgmt_query_goals", "sbmp_tree_query_batch", "sbmp_tree_query_batch_host", "sbmp_goal_radius_threshold",
+    "sbmp_kgmt_recheck_tree", "sbmp_kgmt_query_goals_alive", "sbmp_tree_recheck_batch", "sbmp_tree_recheck_batch_host",
 )
 
 _lib = None
@@ -218,6 +233,10 @@ def lib():
         "sbmp_tree_query_batch": [vp, vp, ctypes.c_longlong, vp, i, vp, vp],
         "sbmp_tree_query_batch_host": [vp, vp, ctypes.c_longlong, vp, i, vp],
         "sbmp_goal_radius_threshold": [ctypes.c_float, P(ctypes.c_float)],
+        "sbmp_kgmt_recheck_tree": [vp, vp, i, vp, i, P(TreeRecheck)],
+        "sbmp_kgmt_query_goals_alive": [vp, vp, i, vp],
+        "sbmp_tree_recheck_batch": [P(TreeRecheckArgs), vp, P(TreeRecheck), vp],
+        "sbmp_tree_recheck_batch_host": [P(TreeRecheckArgs), vp, P(TreeRecheck)],
     }
     for name, args in sig.items():
         f = getattr(L, name)

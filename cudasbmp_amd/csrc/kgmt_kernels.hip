@@ -2154,32 +2154,7 @@ static void launch(K kernel, dim3 grid, dim3 block, size_t shm, hipStream_t s, c
         hipLaunchKernelGGL(kernel, grid, block, shm, s, args...);
 }
 
-// The obstacle form a plan runs (variant: kgmt_launch.h), decided here and nowhere else:
-// f is called with the form as a compile-time constant.
-template <int OBS>
-using ObsForm = std::integral_constant<int, OBS>;
-
-template <typename F>
-static auto with_obs_form(const KgmtDev& d, int variant, F f) {
-    if (d.gridStart) return f(ObsForm<kObsGrid>{});   // the planner built the grid index (large lists, or variant 4)
-    if (d.nObs > kMaxLdsObs) return f(ObsForm<kObsGlobal>{});
-    if (d.nObs <= kMaxRegObs && (variant == 0 || variant == 3)) {
-        switch (d.nObs) {   // the box count is a compile-time constant of the register path
-            case 0: return f(ObsForm<kObsReg + 0>{});
-            case 1: return f(ObsForm<kObsReg + 1>{});
-            case 2: return f(ObsForm<kObsReg + 2>{});
-            case 3: return f(ObsForm<kObsReg + 3>{});
-            case 4: return f(ObsForm<kObsReg + 4>{});
-            case 5: return f(ObsForm<kObsReg + 5>{});
-            case 6: return f(ObsForm<kObsReg + 6>{});
-            case 7: return f(ObsForm<kObsReg + 7>{});
-            default: return f(ObsForm<kObsReg + 8>{});
-        }
-    }
-    if (variant == 2) return f(ObsForm<kObsLds4>{});
-    return f(ObsForm<kObsLds>{});
-}
-
+// The obstacle form a plan runs: with_obs_form (kgmt_launch.h).
 int obstacle_form(const KgmtDev& d, int variant) {
     return with_obs_form(d, variant, [](auto obs) { return obs.value >= kObsReg ? kObsReg : obs.value; });
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "kgmt_device.h"
@@ -22,6 +23,31 @@ struct KernelTiming {
 // The form both launches below run for (d, variant): kObsGrid, kObsGlobal, kObsLds,
 // kObsLds4, or kObsReg for any register list.
 int obstacle_form(const KgmtDev& d, int variant);
+// The obstacle form a plan (or a re-check, tree_recheck.hip) runs for (d, variant), decided
+// here and nowhere else: f is called with the form as a compile-time constant.
+template <int OBS>
+using ObsForm = std::integral_constant<int, OBS>;
+
+template <typename F>
+auto with_obs_form(const KgmtDev& d, int variant, F f) {
+    if (d.gridStart) return f(ObsForm<kObsGrid>{});   // the grid index was built (large lists, or variant 4)
+    if (d.nObs > kMaxLdsObs) return f(ObsForm<kObsGlobal>{});
+    if (d.nObs <= kMaxRegObs && (variant == 0 || variant == 3)) {
+        switch (d.nObs) {   // the box count is a compile-time constant of the register path
+            case 0: return f(ObsForm<kObsReg + 0>{});
+            case 1: return f(ObsForm<kObsReg + 1>{});
+            case 2: return f(ObsForm<kObsReg + 2>{});
+            case 3: return f(ObsForm<kObsReg + 3>{});
+            case 4: return f(ObsForm<kObsReg + 4>{});
+            case 5: return f(ObsForm<kObsReg + 5>{});
+            case 6: return f(ObsForm<kObsReg + 6>{});
+            case 7: return f(ObsForm<kObsReg + 7>{});
+            default: return f(ObsForm<kObsReg + 8>{});
+        }
+    }
+    if (variant == 2) return f(ObsForm<kObsLds4>{});
+    return f(ObsForm<kObsLds>{});
+}
 void launch_expand(const KgmtDev& d, int t, int agent, int blocks, int variant, hipStream_t s,
                    const KernelTiming& tm = KernelTiming());
 // k_fold_r2: add the key log of iterations [tFirst, tLast] (at most kFoldEvery) to R2Valid / R2Invalid.

@@ -575,6 +575,7 @@ KgmtPlanner::~KgmtPlanner() {
     if (poll_) (void)hipHostFree(poll_);
     if (obs_) (void)hipFree(obs_);
     if (dStage_) (void)hipHostFree(dStage_);
+    if (alive_) (void)hipFree(alive_);
     if (gridStart_) (void)hipFree(gridStart_);
     if (gridBoxes_) (void)hipFree(gridBoxes_);
     if (stream_ && ownStream_) (void)hipStreamDestroy(stream_);
@@ -671,6 +672,7 @@ void KgmtPlanner::begin(const float* initial, const float* goal, const float* d_
 
     t_next_ = 1;
     lastFolded_ = 0;
+    aliveRows_ = -1;   // the last re-check's alive mask was of another tree
     begun_ = true;
     wallMs_ = 0.0;
     wallFixed_ = false;
@@ -1177,6 +1179,48 @@ void KgmtPlanner::query_goals(const sbmp_goal_query* goals, int count, sbmp_goal
     const int rows = std::min(std::max(r.treeSize, 1), d_.M);
     tree_query_device(reinterpret_cast<const float*>(d_.treeState), reinterpret_cast<const float*>(d_.treeCtrl), rows,
                       goals, count, out, stream_);
+}
+
+// The tree re-checked against another obstacle list (tree_recheck.hip): behind everything
+// enqueued, reading treeState / treeCtrl / treeParent only.  d_, obs_ and the planner's grid
+// index stay as begin() left them; the new list lives in the call's own copies.
+void KgmtPlanner::recheck_tree(const float* d_obstacles, int nObs, uint8_t* status, int capacity,
+                               sbmp_tree_recheck* out) {
+    if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
+    sbmp_plan_result r;
+    result(&r);   // syncs (the flush pass has inserted the last iteration)
+    const int rows = std::min(std::max(r.treeSize, 1), d_.M);
+    *out = sbmp_tree_recheck{rows, 0, 0, 0, 0, 0, -1};
+    if (status && capacity < rows)
+        throw Error(SBMP_ERR_INVALID_ARGUMENT,
+                    "capacity " + std::to_string(capacity) + " < rows " + std::to_string(rows));
+    aliveRows_ = -1;
+    if (rows > aliveCap_) {
+        if (alive_) SBMP_HIP(hipFree(alive_));
+        alive_ = nullptr;
+        aliveCap_ = 0;
+        SBMP_HIP(hipMalloc(reinterpret_cast<void**>(&alive_), (size_t)rows));
+        aliveCap_ = rows;
+    }
+    // a row inserted by iteration t lies at most t edges below the root
+    tree_recheck_device(d_, p_.agent, expandVariant_, rows, r.iterations + 1, d_obstacles, nObs, alive_, status, out,
+                        stream_);
+    aliveRows_ = rows;
+}
+
+void KgmtPlanner::query_goals_alive(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) {
+    tree_query_check_goals(goals, count, out);
+    if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
+    if (aliveRows_ < 0) throw Error(SBMP_ERR_STATE, "no recheck_tree since the last begin()");
+    sbmp_plan_result r;
+    result(&r);   // syncs
+    const int rows = std::min(std::max(r.treeSize, 1), d_.M);
+    if (rows != aliveRows_)
+        throw Error(SBMP_ERR_STATE, "the tree has " + std::to_string(rows) + " rows, the last recheck_tree covered " +
+                                        std::to_string(aliveRows_) + ": re-check again");
+    if (count == 0) return;
+    tree_query_alive_device(reinterpret_cast<const float*>(d_.treeState), reinterpret_cast<const float*>(d_.treeCtrl),
+                            alive_, rows, goals, count, out, stream_);
 }
 
 unsigned long long* KgmtPlanner::alloc_scratch_u64() {

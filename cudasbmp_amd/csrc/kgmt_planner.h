@@ -86,6 +86,13 @@ public:
     // out[i] answers goals[i] over the rows copy_tree exports, [0, min(treeSize, M)), after
     // everything enqueued has finished (k_tree_query; reads the tree only).
     virtual void query_goals(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) = 0;
+    // The rows [0, min(treeSize, M)) re-checked against another obstacle list (k_tree_recheck,
+    // k_tree_alive; include/sbmp/tree_recheck.h): status is host memory of `capacity` bytes or
+    // null; the alive mask stays with the planner until the next begin().  Reads the tree only.
+    virtual void recheck_tree(const float* d_obstacles, int nObs, uint8_t* status, int capacity,
+                              sbmp_tree_recheck* out) = 0;
+    // query_goals over the rows the last recheck_tree left alive.
+    virtual void query_goals_alive(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) = 0;
     void export_csv(const std::string& dir);
 
     virtual std::vector<sbmp_kernel_stat> kernel_stats() = 0;
@@ -112,6 +119,20 @@ void tree_query_device(const float* d_state, const float* d_ctrl, long long rows
                        int count, sbmp_goal_answer* out, hipStream_t stream);
 void tree_query_host(const float* state, const float* ctrl, long long rows, const sbmp_goal_query* goals, int count,
                      sbmp_goal_answer* out);
+sbmp_goal_answer goal_answer_of(unsigned count, unsigned first, unsigned long long best, unsigned long long nearest);
+
+// The tree re-check (tree_recheck.hip; include/sbmp/tree_recheck.h).  base: the plan's
+// parameters and tree pointers; only a copy with the obstacle fields replaced reaches the
+// kernels.  d_alive: `rows` device bytes that receive the alive mask, or null.  status: host,
+// `rows` bytes, or null.  Runs on `stream` and waits for the result; scratch is per call.
+void tree_recheck_device(const KgmtDev& base, int agent, int variant, int rows, int depthBound,
+                         const float* d_obstacles, int nObs, uint8_t* d_alive, uint8_t* status,
+                         sbmp_tree_recheck* out, hipStream_t stream);
+void tree_recheck_batch(const sbmp_tree_recheck_args* a, uint8_t* status, sbmp_tree_recheck* out, hipStream_t stream);
+void tree_recheck_batch_host(const sbmp_tree_recheck_args* a, uint8_t* status, sbmp_tree_recheck* out);
+// k_tree_query_alive: tree_query_device over the rows whose d_alive byte is set.
+void tree_query_alive_device(const float* d_state, const float* d_ctrl, const uint8_t* d_alive, long long rows,
+                             const sbmp_goal_query* goals, int count, sbmp_goal_answer* out, hipStream_t stream);
 
 // Times kernel launches of `ids` kinds with event pairs: the pairs are handed to
 // hipExtLaunchKernelGGL, which stamps them with the kernel's own start/end.
@@ -198,6 +219,9 @@ public:
     int solution_path(int node, int* rows, float* samples, float* costs, int capacity) override;
     unsigned long long state_hash() override;
     void query_goals(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) override;
+    void recheck_tree(const float* d_obstacles, int nObs, uint8_t* status, int capacity,
+                      sbmp_tree_recheck* out) override;
+    void query_goals_alive(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) override;
 
     std::vector<sbmp_kernel_stat> kernel_stats() override;
     void path_info(sbmp_path_info* out) override;
@@ -291,6 +315,9 @@ private:
     std::vector<void*> allocs_;
     unsigned long long* scratch_ = nullptr;   // 8 device words for small results (state_hash)
     unsigned long long* alloc_scratch_u64();
+    uint8_t* alive_ = nullptr;   // recheck_tree's alive mask, one byte per row of [0, aliveRows_)
+    int aliveCap_ = 0;
+    int aliveRows_ = -1;         // -1: no re-check since the last begin()
     double wallMs_ = 0.0;
     double t0_ = 0.0;
     LaunchTimer timer_{K_COUNT};
@@ -338,6 +365,15 @@ public:
     void query_goals(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) override {
         sync();
         r0().query_goals(goals, count, out);   // every rank holds the whole tree
+    }
+    void recheck_tree(const float* d_obstacles, int nObs, uint8_t* status, int capacity,
+                      sbmp_tree_recheck* out) override {
+        sync();
+        r0().recheck_tree(d_obstacles, nObs, status, capacity, out);
+    }
+    void query_goals_alive(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) override {
+        sync();
+        r0().query_goals_alive(goals, count, out);
     }
 
     std::vector<sbmp_kernel_stat> kernel_stats() override { return r0().kernel_stats(); }

@@ -203,6 +203,16 @@ sbmp_status sbmp_tree_query_batch_host(const float* state, const float* ctrl, lo
     return guarded([&] { sbmp::tree_query_host(state, ctrl, rows, goals, count, out); });
 }
 
+sbmp_status sbmp_tree_recheck_batch(const sbmp_tree_recheck_args* args, uint8_t* status, sbmp_tree_recheck* out,
+                                    void* stream) {
+    return guarded([&] { sbmp::tree_recheck_batch(args, status, out, static_cast<hipStream_t>(stream)); });
+}
+
+sbmp_status sbmp_tree_recheck_batch_host(const sbmp_tree_recheck_args* args, uint8_t* status,
+                                         sbmp_tree_recheck* out) {
+    return guarded([&] { sbmp::tree_recheck_batch_host(args, status, out); });
+}
+
 sbmp_status sbmp_goal_radius_threshold(float r, float* t) {
     return guarded([&] {
         REQUIRE(t, "t must be non-NULL");
@@ -398,6 +408,25 @@ sbmp_status sbmp_kgmt_query_goals(sbmp_kgmt* h, const sbmp_goal_query* goals, in
     return guarded([&] {
         PLANNER(h);
         P.query_goals(goals, count, out);
+    });
+}
+
+sbmp_status sbmp_kgmt_recheck_tree(sbmp_kgmt* h, const float* d_obstacles, int obstaclesCount, uint8_t* status,
+                                   int capacity, sbmp_tree_recheck* out) {
+    return guarded([&] {
+        PLANNER(h);
+        REQUIRE(out, "out must be non-NULL");
+        REQUIRE(obstaclesCount >= 0, "obstaclesCount must be >= 0");
+        REQUIRE(obstaclesCount == 0 || d_obstacles, "NULL obstacle list with obstaclesCount > 0");
+        P.recheck_tree(d_obstacles, obstaclesCount, status, capacity, out);
+    });
+}
+
+sbmp_status sbmp_kgmt_query_goals_alive(sbmp_kgmt* h, const sbmp_goal_query* goals, int count,
+                                        sbmp_goal_answer* out) {
+    return guarded([&] {
+        PLANNER(h);
+        P.query_goals_alive(goals, count, out);
     });
 }
 

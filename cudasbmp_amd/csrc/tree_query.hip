@@ -214,7 +214,9 @@ void check_query_rows(const void* state, const void* ctrl, long long rows) {
     if (rows < 1 || rows > 0x7fffffffll) throw Error(SBMP_ERR_INVALID_ARGUMENT, "rows must be in [1, 2^31)");
 }
 
-sbmp_goal_answer answer_of(unsigned count, unsigned first, unsigned long long best, unsigned long long nearest) {
+}  // namespace
+
+sbmp_goal_answer goal_answer_of(unsigned count, unsigned first, unsigned long long best, unsigned long long nearest) {
     sbmp_goal_answer a;
     a.count = (int)count;
     a.firstRow = count ? (int)first : -1;
@@ -224,7 +226,6 @@ sbmp_goal_answer answer_of(unsigned count, unsigned first, unsigned long long be
     a.nearestDistance = __builtin_sqrtf(u2f((uint32_t)(nearest >> 32)));
     return a;
 }
-}  // namespace
 
 void launch_tree_query(const float4* state, const float4* ctrl, long long rows, const float* goalsXYT, int count,
                        QueryAcc* acc, hipStream_t s) {
@@ -287,7 +288,7 @@ void tree_query_device(const float* d_state, const float* d_ctrl, long long rows
     }
     (void)hipFree(acc);
     SBMP_HIP(e);
-    for (int i = 0; i < count; ++i) out[i] = answer_of(host[i].count, host[i].first, host[i].best, host[i].nearest);
+    for (int i = 0; i < count; ++i) out[i] = goal_answer_of(host[i].count, host[i].first, host[i].best, host[i].nearest);
 }
 
 // The literal rule, row by row (no threshold): what the kernel must reproduce.
@@ -308,7 +309,7 @@ void tree_query_host(const float* state, const float* ctrl, long long rows, cons
             const unsigned long long bk = goal_key(ctrl[4 * row + 3], (uint32_t)row);
             if (bk < best) best = bk;
         }
-        out[i] = answer_of(n, first, best, nearest);
+        out[i] = goal_answer_of(n, first, best, nearest);
     }
 }
 

@@ -279,17 +279,43 @@ class KGMT:
                      s.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n))
         return rows, s, c
 
-    def query_goals(self, goals, radius=None) -> dict:
+    def query_goals(self, goals, radius=None, alive: bool = False) -> dict:
         """Goal discs against the tree as it stands (sbmp_kgmt_query_goals; one k_tree_query pass
         per 16 goals): goals is (Q, 2) with one radius for all, or (Q, 3) rows of (x, y, radius).
         Returns (Q,) arrays count, firstRow, bestRow, bestCost, nearestRow, nearestDistance over
-        the rows tree() exports; the plan goes on unchanged."""
+        the rows tree() exports; the plan goes on unchanged.  alive=True: over the rows the last
+        recheck() left alive only (sbmp_kgmt_query_goals_alive); row numbers stay the tree's own."""
         from .tree_query import ANSWER_DTYPE, answers_dict, goal_array
         g = goal_array(goals, radius)
         out = np.zeros(max(1, len(g)), dtype=ANSWER_DTYPE)
-        nat.call("sbmp_kgmt_query_goals", self._h, g.ctypes.data_as(ctypes.c_void_p), len(g),
-                 out.ctypes.data_as(ctypes.c_void_p))
+        nat.call("sbmp_kgmt_query_goals_alive" if alive else "sbmp_kgmt_query_goals", self._h,
+                 g.ctypes.data_as(ctypes.c_void_p), len(g), out.ctypes.data_as(ctypes.c_void_p))
         return answers_dict(out[: len(g)])
+
+    def recheck(self, obstacles, obstaclesCount: Optional[int] = None):
+        """The tree as it stands re-checked against another obstacle list (sbmp_kgmt_recheck_tree;
+        include/sbmp/tree_recheck.h): obstacles is an (n, 4) array, or a device pointer with
+        obstaclesCount as plan() takes them.  Returns (status, summary): one byte per row of
+        tree() up to min(treeSize, M) (SBMP_ROW_*; bit 7, SBMP_ROW_CUT, on a free row below a dead
+        one) and a dict rows, alive, blocked, stale, orphan, cut, firstDead.  The plan, its own
+        obstacle list and what it goes on to compute are unchanged."""
+        s = nat.TreeRecheck()
+        own = None
+        try:
+            if obstaclesCount is None:
+                boxes = np.ascontiguousarray(obstacles, dtype=np.float32).reshape(-1, 4)
+                obstaclesCount = len(boxes)
+                own = DeviceBuffer(boxes) if obstaclesCount else None
+                ptr = own.ptr if own is not None else None
+            else:
+                ptr = device_ptr(obstacles) if obstaclesCount else None
+            status = np.zeros(max(1, self.M), dtype=np.uint8)
+            nat.call("sbmp_kgmt_recheck_tree", self._h, ctypes.c_void_p(ptr), int(obstaclesCount),
+                     status.ctypes.data_as(ctypes.c_void_p), len(status), ctypes.byref(s))
+        finally:
+            if own is not None:
+                own.free()
+        return status[: s.rows].copy(), {k: getattr(s, k) for k, _ in nat.TreeRecheck._fields_}
 
     def unexplored(self):
         M = self.M

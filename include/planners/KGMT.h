@@ -123,6 +123,23 @@ public:
         SBMP_CHECK(sbmp_kgmt_query_goals(h_, goals.data(), (int)goals.size(), out.data()));
         return out;
     }
+    // The tree as it stands re-checked against another obstacle list in device memory
+    // (sbmp_kgmt_recheck_tree; sbmp/tree_recheck.h): one SBMP_ROW_* byte per row into status
+    // (resized to the rows covered) and the summary.  The plan and its own list are unchanged.
+    sbmp_tree_recheck recheckTree(const float* d_obstacles, int obstaclesCount, std::vector<uint8_t>* status = nullptr) const {
+        sbmp_tree_recheck s{};
+        if (status) status->assign((size_t)(maxTreeSize_ > 0 ? maxTreeSize_ : 1), 0);
+        SBMP_CHECK(sbmp_kgmt_recheck_tree(h_, d_obstacles, obstaclesCount, status ? status->data() : nullptr,
+                                          status ? (int)status->size() : 0, &s));
+        if (status) status->resize((size_t)s.rows);
+        return s;
+    }
+    // queryGoals over the rows the last recheckTree left alive (sbmp_kgmt_query_goals_alive).
+    std::vector<sbmp_goal_answer> queryGoalsAlive(const std::vector<sbmp_goal_query>& goals) const {
+        std::vector<sbmp_goal_answer> out(goals.size());
+        SBMP_CHECK(sbmp_kgmt_query_goals_alive(h_, goals.data(), (int)goals.size(), out.data()));
+        return out;
+    }
     sbmp_kgmt* handle() const { return h_; }
 
     // Public fields of KGMT.cuh:33-43 that carry meaning outside the class.

@@ -24,13 +24,19 @@
 
 namespace sbmp {
 
-// reference statePropagator.cu:5-76
-SBMP_HD bool propagateAndCheck(const float* x0, float* x1, int numDisc, float agentLength, Xorwow* state,
-                               const float* obstacles, int obstaclesCount, float width, float height) {
-    const float a = __builtin_fmaf(xorwow_uniform(*state), 10.0f, -5.0f);
+// The three draws of statePropagator.cu:17-21, in the reference's order.
+SBMP_HD void drawCarControls(Xorwow* state, float* a, float* steering, float* duration) {
+    *a = __builtin_fmaf(xorwow_uniform(*state), 10.0f, -5.0f);
     const float u2 = xorwow_uniform(*state);
-    const float steering = (float)__builtin_fma((double)(u2 * 2.0f), 3.141592653589793, -3.141592653589793);
-    const float duration = __builtin_fmaf(xorwow_uniform(*state), 1.0f, 0.05f);
+    *steering = (float)__builtin_fma((double)(u2 * 2.0f), 3.141592653589793, -3.141592653589793);
+    *duration = __builtin_fmaf(xorwow_uniform(*state), 1.0f, 0.05f);
+}
+
+// statePropagator.cu:22-76 with the controls given: what propagateAndCheck runs behind its
+// draws, and what a replay of a stored tree row runs (include/sbmp/tree_recheck.h).
+SBMP_HD bool propagateCarControls(const float* x0, float* x1, int numDisc, float agentLength, float a, float steering,
+                                  float duration, const float* obstacles, int obstaclesCount, float width,
+                                  float height) {
     const float dt = duration / (float)numDisc;
     float x = x0[0], y = x0[1], theta = x0[2], v = x0[3];
     const float tan_steering = tanf_d(steering);
@@ -66,15 +72,28 @@ SBMP_HD bool propagateAndCheck(const float* x0, float* x1, int numDisc, float ag
     return motionValid;
 }
 
+// reference statePropagator.cu:5-76
+SBMP_HD bool propagateAndCheck(const float* x0, float* x1, int numDisc, float agentLength, Xorwow* state,
+                               const float* obstacles, int obstaclesCount, float width, float height) {
+    float a, steering, duration;
+    drawCarControls(state, &a, &steering, &duration);
+    return propagateCarControls(x0, x1, numDisc, agentLength, a, steering, duration, obstacles, obstaclesCount, width,
+                                height);
+}
+
 // Build extension, no reference counterpart: a
 // holonomic R2 point in the same skeleton.  Controls (vx, vy) in (-1, 1]^2, the
 // duration as the car's; x += vx dt, y += vy dt with the same per-step bounds and
 // collision checks; x1 = [x, y, 0, 0, vx, vy, duration].
-SBMP_HD bool propagatePoint(const float* x0, float* x1, int numDisc, Xorwow* state, const float* obstacles,
-                            int obstaclesCount, float width, float height) {
-    const float vx = __builtin_fmaf(xorwow_uniform(*state), 2.0f, -1.0f);
-    const float vy = __builtin_fmaf(xorwow_uniform(*state), 2.0f, -1.0f);
-    const float duration = __builtin_fmaf(xorwow_uniform(*state), 1.0f, 0.05f);
+SBMP_HD void drawPointControls(Xorwow* state, float* vx, float* vy, float* duration) {
+    *vx = __builtin_fmaf(xorwow_uniform(*state), 2.0f, -1.0f);
+    *vy = __builtin_fmaf(xorwow_uniform(*state), 2.0f, -1.0f);
+    *duration = __builtin_fmaf(xorwow_uniform(*state), 1.0f, 0.05f);
+}
+
+// propagatePoint behind its draws (see propagateCarControls).
+SBMP_HD bool propagatePointControls(const float* x0, float* x1, int numDisc, float vx, float vy, float duration,
+                                    const float* obstacles, int obstaclesCount, float width, float height) {
     const float dt = duration / (float)numDisc;
     float x = x0[0], y = x0[1];
     bool motionValid = true;
@@ -103,6 +122,14 @@ SBMP_HD bool propagatePoint(const float* x0, float* x1, int numDisc, Xorwow* sta
     x1[5] = vy;
     x1[6] = duration;
     return motionValid;
+}
+
+// The point's propagator: its three draws, then the controls-given body.
+SBMP_HD bool propagatePoint(const float* x0, float* x1, int numDisc, Xorwow* state, const float* obstacles,
+                            int obstaclesCount, float width, float height) {
+    float vx, vy, duration;
+    drawPointControls(state, &vx, &vy, &duration);
+    return propagatePointControls(x0, x1, numDisc, vx, vy, duration, obstacles, obstaclesCount, width, height);
 }
 
 }  // namespace sbmp

@@ -252,6 +252,45 @@ typedef struct sbmp_goal_answer {
  * or a goal with a non-finite x or y: SBMP_ERR_INVALID_ARGUMENT.  count == 0 is a no-op. */
 sbmp_status sbmp_kgmt_query_goals(sbmp_kgmt* h, const sbmp_goal_query* goals, int count, sbmp_goal_answer* out);
 
+/* Re-check of the tree as it stands against another obstacle list (include/sbmp/tree_recheck.h
+ * states the rule; no reference counterpart).  Every row r of [0, rows),
+ * rows = min(treeSize, maxTreeSize), gets one status byte, the first matching rule:
+ *   SBMP_ROW_FREE     r == 0 (the root has no edge), or the replay of treeState[parent] with
+ *                     the row's stored (a, steering, duration) runs all numDisc steps valid
+ *                     under the new list and ends on the stored state bit for bit
+ *   SBMP_ROW_ORPHAN   r > 0 and parent is not in [0, r) (nothing is read through it)
+ *   SBMP_ROW_BLOCKED  the replay meets a box of the new list or leaves the workspace
+ *   SBMP_ROW_STALE    the replay stays valid but does not end on the stored state
+ * A row is alive iff it is FREE and its parent is alive (row 0: iff FREE, i.e. always).
+ * A FREE row that is not alive is exported with SBMP_ROW_CUT set. */
+#define SBMP_ROW_FREE 0
+#define SBMP_ROW_ORPHAN 1
+#define SBMP_ROW_BLOCKED 2
+#define SBMP_ROW_STALE 3
+#define SBMP_ROW_CUT 0x80
+typedef struct sbmp_tree_recheck {
+    int rows, alive, blocked, stale, orphan, cut;   /* rows = alive + blocked + stale + orphan + cut */
+    int firstDead;                                  /* lowest row not alive, -1 if none */
+} sbmp_tree_recheck;
+/* d_obstacles: obstaclesCount boxes (xmin, ymin, xmax, ymax) in device memory, as plan()
+ * takes them; the planner's own list, obstacle form and grid index are not touched, and the
+ * plan goes on unchanged (the call only reads the tree; it waits for everything enqueued, like
+ * sbmp_kgmt_state_hash, and runs on the planner's stream).  status: host array of `capacity`
+ * bytes or NULL.  out->rows is set in every case, so a NULL / 0 call still re-checks and
+ * returns the summary.  The alive mask stays with the planner until the next begin()
+ * (sbmp_kgmt_query_goals_alive).  Valid after plan() and between step() calls, on a local
+ * shard group (rank 0 answers), a sharded rank (its own replica) and a batch member.
+ * Before the first begin(): SBMP_ERR_STATE.  obstaclesCount < 0, a NULL list with
+ * obstaclesCount > 0, out NULL, or status given with capacity < rows: SBMP_ERR_INVALID_ARGUMENT. */
+sbmp_status sbmp_kgmt_recheck_tree(sbmp_kgmt* h, const float* d_obstacles, int obstaclesCount, uint8_t* status,
+                                   int capacity, sbmp_tree_recheck* out);
+/* sbmp_kgmt_query_goals with every row that is not alive treated as absent (count, firstRow,
+ * bestRow and nearestRow alike; row numbers are the tree's own).  SBMP_ERR_STATE without a
+ * re-check since the last begin(), or when min(treeSize, maxTreeSize) no longer equals the
+ * re-check's rows (the tree grew: re-check again). */
+sbmp_status sbmp_kgmt_query_goals_alive(sbmp_kgmt* h, const sbmp_goal_query* goals, int count,
+                                        sbmp_goal_answer* out);
+
 sbmp_status sbmp_kgmt_kernel_stats(sbmp_kgmt* h, sbmp_kernel_stat* out, int capacity, int* count);
 /* The form of the hot path chosen at the last begin() (sbmp_path_info). */
 sbmp_status sbmp_kgmt_path_info(sbmp_kgmt* h, sbmp_path_info* out);
@@ -367,6 +406,34 @@ sbmp_status sbmp_tree_query_batch(const float* d_state, const float* d_ctrl, lon
                                   void* stream /* hipStream_t; NULL: default */);
 sbmp_status sbmp_tree_query_batch_host(const float* state, const float* ctrl, long long rows,
                                        const sbmp_goal_query* goals, int count, sbmp_goal_answer* out);
+/* sbmp_tree_recheck_batch: the re-check of sbmp_kgmt_recheck_tree (k_tree_recheck, k_tree_alive)
+ * over caller rows in the planner's tree layout: state rows x 4 floats (x, y, theta, v), ctrl
+ * rows x 4 floats (a, steering, duration, -; a point agent: vx, vy, duration, -), parent rows
+ * ints, and obstaclesCount boxes; all four in device memory.  1 <= rows < 2^31; states and
+ * controls are finite, a car's steering lies in (-pi, pi] as the planner draws it (D11).  depthBound: an upper bound on the rows of any parent chain (the
+ * planner's is its executed iterations + 1), which sets the number of pointer-jumping passes;
+ * <= 0: rows, always sufficient because a usable parent is a lower row.  status (host, rows
+ * bytes, may be NULL) and *out as sbmp_kgmt_recheck_tree.  Waits for the result.
+ * sbmp_tree_recheck_batch_host takes the same arrays in host memory and applies the literal
+ * rule in one ascending loop (propagateCarControls / propagatePointControls of
+ * include/sbmp/propagator.h): a second statement of the rule, and it needs no device. */
+typedef struct sbmp_tree_recheck_args {
+    const float* state;
+    const float* ctrl;
+    const int* parent;
+    int rows;
+    int depthBound;
+    int agent;                /* SBMP_AGENT_* */
+    int numDisc;
+    float agentLength, width, height;
+    const float* obstacles;
+    int obstaclesCount;
+} sbmp_tree_recheck_args;
+sbmp_status sbmp_tree_recheck_batch(const sbmp_tree_recheck_args* args, uint8_t* status, sbmp_tree_recheck* out,
+                                    void* stream /* hipStream_t; NULL: default */);
+sbmp_status sbmp_tree_recheck_batch_host(const sbmp_tree_recheck_args* args, uint8_t* status,
+                                         sbmp_tree_recheck* out);
+
 /* The threshold the kernel compares d2 with (host-only, no device needed): *t = the largest
  * float d2 with sqrtf(d2) < r, found by bisecting the float bit patterns with that rule;
  * FLT_MAX for r = +inf; -1 (no d2 is inside) for r <= 0 and for NaN. */
@@ -440,7 +507,7 @@ sbmp_status sbmp_kgmt_batch_enqueue(sbmp_kgmt_batch* h, int iterations);
 sbmp_status sbmp_kgmt_batch_sync(sbmp_kgmt_batch* h);
 sbmp_status sbmp_kgmt_batch_result(sbmp_kgmt_batch* h, int member, sbmp_plan_result* result);
 /* Member i as a planner handle owned by the batch, for every read-only call above
- * (copy_tree, copy_regions, copy_rng, iter_log, solution_path, query_goals, state_hash,
+ * (copy_tree, copy_regions, copy_rng, iter_log, solution_path, query_goals, recheck_tree, query_goals_alive, state_hash,
  * export_csv, path_info, kernel_stats, ...).  sbmp_kgmt_plan / begin / step / enqueue / destroy on it fail
  * with SBMP_ERR_STATE, sbmp_kgmt_set_iteration_dump with SBMP_ERR_UNSUPPORTED. */
 sbmp_status sbmp_kgmt_batch_member(sbmp_kgmt_batch* h, int i, sbmp_kgmt** borrowed);
