@@ -122,6 +122,15 @@ class TreeRecheckArgs(ctypes.Structure):   # sbmp_tree_recheck_args
 SBMP_ROW_FREE, SBMP_ROW_ORPHAN, SBMP_ROW_BLOCKED, SBMP_ROW_STALE, SBMP_ROW_CUT = 0, 1, 2, 3, 0x80
 
 
+class TreePathsArgs(ctypes.Structure):   # sbmp_tree_paths_args
+    _fields_ = [("state", ctypes.c_void_p), ("ctrl", ctypes.c_void_p), ("parent", ctypes.c_void_p),
+                ("rows", ctypes.c_int), ("depthBound", ctypes.c_int), ("agent", ctypes.c_int),
+                ("numDisc", ctypes.c_int), ("agentLength", ctypes.c_float)]
+
+
+SBMP_PATH_OK, SBMP_PATH_NONE, SBMP_PATH_BROKEN, SBMP_PATH_DEEP = 0, 1, 2, 3
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", ctypes.c_longlong), ("totalMs", ctypes.c_double)]
 
@@ -146,6 +155,8 @@ EXPORTED_SYMBOLS = (
     "sbmp_division_reciprocal",
     "sbmp_kgmt_query_goals", "sbmp_tree_query_batch", "sbmp_tree_query_batch_host", "sbmp_goal_radius_threshold",
     "sbmp_kgmt_recheck_tree", "sbmp_kgmt_query_goals_alive", "sbmp_tree_recheck_batch", "sbmp_tree_recheck_batch_host",
+    "sbmp_kgmt_solution_paths", "sbmp_kgmt_trace_rows", "sbmp_tree_paths_batch", "sbmp_tree_paths_batch_host",
+    "sbmp_tree_trace_batch", "sbmp_tree_trace_batch_host",
 )
 
 _lib = None
@@ -237,6 +248,14 @@ def lib():
         "sbmp_kgmt_query_goals_alive": [vp, vp, i, vp],
         "sbmp_tree_recheck_batch": [P(TreeRecheckArgs), vp, P(TreeRecheck), vp],
         "sbmp_tree_recheck_batch_host": [P(TreeRecheckArgs), vp, P(TreeRecheck)],
+        "sbmp_kgmt_solution_paths": [vp, vp, i, vp, vp, vp, vp, vp, ctypes.c_longlong, P(ctypes.c_longlong)],
+        "sbmp_kgmt_trace_rows": [vp, vp, ctypes.c_longlong, vp, vp],
+        "sbmp_tree_paths_batch": [P(TreePathsArgs), vp, i, vp, vp, vp, vp, vp, ctypes.c_longlong,
+                                  P(ctypes.c_longlong), vp],
+        "sbmp_tree_paths_batch_host": [P(TreePathsArgs), vp, i, vp, vp, vp, vp, vp, ctypes.c_longlong,
+                                       P(ctypes.c_longlong)],
+        "sbmp_tree_trace_batch": [P(TreePathsArgs), vp, ctypes.c_longlong, vp, vp, vp],
+        "sbmp_tree_trace_batch_host": [P(TreePathsArgs), vp, ctypes.c_longlong, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -1223,6 +1223,35 @@ void KgmtPlanner::query_goals_alive(const sbmp_goal_query* goals, int count, sbm
                             alive_, rows, goals, count, out, stream_);
 }
 
+// Many parent chains and the Euler steps of listed rows (tree_paths.hip): behind everything
+// enqueued, reading treeState / treeCtrl / treeParent only, into buffers of the call's own.
+void KgmtPlanner::solution_paths(const int* nodes, int count, int* lengths, uint8_t* status, int* rows,
+                                 float* samples, float* costs, long long capacity, long long* total) {
+    if (!total) throw Error(SBMP_ERR_INVALID_ARGUMENT, "total must be non-NULL");
+    *total = 0;
+    if (count < 0 || (count > 0 && !nodes)) throw Error(SBMP_ERR_INVALID_ARGUMENT, "bad node list");
+    if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
+    if (count == 0) return;
+    sbmp_plan_result r;
+    result(&r);   // syncs (the flush pass has inserted the last iteration)
+    const int R = std::min(std::max(r.treeSize, 1), d_.M);
+    tree_paths_check(nodes, count, R, total);
+    // one level per iteration, plus the root: solution_path's bound
+    tree_paths_device(d_, R, p_.numIterations + 2, nodes, count, lengths, status, rows, samples, costs, capacity, total,
+                      stream_);
+}
+
+void KgmtPlanner::trace_rows(const int* rows, long long count, float* steps, uint8_t* status) {
+    if (count < 0) throw Error(SBMP_ERR_INVALID_ARGUMENT, "count must be >= 0");
+    if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
+    if (count == 0) return;
+    sbmp_plan_result r;
+    result(&r);   // syncs
+    const int R = std::min(std::max(r.treeSize, 1), d_.M);
+    tree_trace_check(rows, count, R, steps);
+    tree_trace_to_host(d_, p_.agent, R, rows, count, steps, status, stream_);
+}
+
 unsigned long long* KgmtPlanner::alloc_scratch_u64() {
     if (!scratch_) scratch_ = alloc<unsigned long long>(8);
     return scratch_;

@@ -93,6 +93,12 @@ public:
                               sbmp_tree_recheck* out) = 0;
     // query_goals over the rows the last recheck_tree left alive.
     virtual void query_goals_alive(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) = 0;
+    // Many parent chains and the Euler steps of listed rows over [0, min(treeSize, M)) (k_path_walk,
+    // k_tree_trace; include/sbmp/tree_paths.h), as sbmp_kgmt_solution_paths / sbmp_kgmt_trace_rows
+    // take them: host arrays, *total set before a capacity error.  They read the tree only.
+    virtual void solution_paths(const int* nodes, int count, int* lengths, uint8_t* status, int* rows, float* samples,
+                                float* costs, long long capacity, long long* total) = 0;
+    virtual void trace_rows(const int* rows, long long count, float* steps, uint8_t* status) = 0;
     void export_csv(const std::string& dir);
 
     virtual std::vector<sbmp_kernel_stat> kernel_stats() = 0;
@@ -133,6 +139,30 @@ void tree_recheck_batch_host(const sbmp_tree_recheck_args* a, uint8_t* status, s
 // k_tree_query_alive: tree_query_device over the rows whose d_alive byte is set.
 void tree_query_alive_device(const float* d_state, const float* d_ctrl, const uint8_t* d_alive, long long rows,
                              const sbmp_goal_query* goals, int count, sbmp_goal_answer* out, hipStream_t stream);
+
+// Paths and traces (tree_paths.hip; include/sbmp/tree_paths.h).  d: the tree pointers and, for
+// the trace, numDisc / agentLength and their reciprocals; `rows` rows.  tree_paths_device: nodes
+// and every output are host memory (checked by the caller: tree_paths_check); *total is set
+// before a capacity error.  tree_trace_device: d_list (or null), d_steps and d_status are
+// device memory, the list already checked.  Both run on `stream` and wait for the result.
+void tree_paths_check(const int* nodes, int count, int rows, const long long* total);
+void tree_paths_device(const KgmtDev& d, int rows, int depthBound, const int* nodes, int count, int* lengths,
+                       uint8_t* status, int* outRows, float* samples, float* costs, long long capacity,
+                       long long* total, hipStream_t stream);
+void tree_trace_check(const int* list, long long count, int rows, const float* steps);
+void tree_trace_device(const KgmtDev& d, int agent, int rows, const int* d_list, long long count, float* d_steps,
+                       uint8_t* d_status, hipStream_t stream);
+// host list and outputs: the device buffers are the call's own
+void tree_trace_to_host(const KgmtDev& d, int agent, int rows, const int* list, long long count, float* steps,
+                        uint8_t* status, hipStream_t stream);
+void tree_paths_batch(const sbmp_tree_paths_args* a, const int* nodes, int count, int* lengths, uint8_t* status,
+                      int* rows, float* samples, float* costs, long long capacity, long long* total, hipStream_t stream);
+void tree_paths_batch_host(const sbmp_tree_paths_args* a, const int* nodes, int count, int* lengths, uint8_t* status,
+                           int* rows, float* samples, float* costs, long long capacity, long long* total);
+void tree_trace_batch(const sbmp_tree_paths_args* a, const int* d_rows, long long count, float* d_steps,
+                      uint8_t* d_status, hipStream_t stream);
+void tree_trace_batch_host(const sbmp_tree_paths_args* a, const int* rows, long long count, float* steps,
+                           uint8_t* status);
 
 // Times kernel launches of `ids` kinds with event pairs: the pairs are handed to
 // hipExtLaunchKernelGGL, which stamps them with the kernel's own start/end.
@@ -222,6 +252,9 @@ public:
     void recheck_tree(const float* d_obstacles, int nObs, uint8_t* status, int capacity,
                       sbmp_tree_recheck* out) override;
     void query_goals_alive(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) override;
+    void solution_paths(const int* nodes, int count, int* lengths, uint8_t* status, int* rows, float* samples,
+                        float* costs, long long capacity, long long* total) override;
+    void trace_rows(const int* rows, long long count, float* steps, uint8_t* status) override;
 
     std::vector<sbmp_kernel_stat> kernel_stats() override;
     void path_info(sbmp_path_info* out) override;
@@ -374,6 +407,15 @@ public:
     void query_goals_alive(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) override {
         sync();
         r0().query_goals_alive(goals, count, out);
+    }
+    void solution_paths(const int* nodes, int count, int* lengths, uint8_t* status, int* rows, float* samples,
+                        float* costs, long long capacity, long long* total) override {
+        sync();
+        r0().solution_paths(nodes, count, lengths, status, rows, samples, costs, capacity, total);
+    }
+    void trace_rows(const int* rows, long long count, float* steps, uint8_t* status) override {
+        sync();
+        r0().trace_rows(rows, count, steps, status);
     }
 
     std::vector<sbmp_kernel_stat> kernel_stats() override { return r0().kernel_stats(); }

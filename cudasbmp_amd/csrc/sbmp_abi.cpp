@@ -213,6 +213,33 @@ sbmp_status sbmp_tree_recheck_batch_host(const sbmp_tree_recheck_args* args, uin
     return guarded([&] { sbmp::tree_recheck_batch_host(args, status, out); });
 }
 
+sbmp_status sbmp_tree_paths_batch(const sbmp_tree_paths_args* args, const int* nodes, int count, int* lengths,
+                                  uint8_t* status, int* rows, float* samples, float* costs, long long capacity,
+                                  long long* total, void* stream) {
+    return guarded([&] {
+        sbmp::tree_paths_batch(args, nodes, count, lengths, status, rows, samples, costs, capacity, total,
+                               static_cast<hipStream_t>(stream));
+    });
+}
+
+sbmp_status sbmp_tree_paths_batch_host(const sbmp_tree_paths_args* args, const int* nodes, int count, int* lengths,
+                                       uint8_t* status, int* rows, float* samples, float* costs, long long capacity,
+                                       long long* total) {
+    return guarded(
+        [&] { sbmp::tree_paths_batch_host(args, nodes, count, lengths, status, rows, samples, costs, capacity, total); });
+}
+
+sbmp_status sbmp_tree_trace_batch(const sbmp_tree_paths_args* args, const int* d_rows, long long count,
+                                  float* d_steps, uint8_t* d_status, void* stream) {
+    return guarded(
+        [&] { sbmp::tree_trace_batch(args, d_rows, count, d_steps, d_status, static_cast<hipStream_t>(stream)); });
+}
+
+sbmp_status sbmp_tree_trace_batch_host(const sbmp_tree_paths_args* args, const int* rows, long long count,
+                                       float* steps, uint8_t* status) {
+    return guarded([&] { sbmp::tree_trace_batch_host(args, rows, count, steps, status); });
+}
+
 sbmp_status sbmp_goal_radius_threshold(float r, float* t) {
     return guarded([&] {
         REQUIRE(t, "t must be non-NULL");
@@ -427,6 +454,21 @@ sbmp_status sbmp_kgmt_query_goals_alive(sbmp_kgmt* h, const sbmp_goal_query* goa
     return guarded([&] {
         PLANNER(h);
         P.query_goals_alive(goals, count, out);
+    });
+}
+
+sbmp_status sbmp_kgmt_solution_paths(sbmp_kgmt* h, const int* nodes, int count, int* lengths, uint8_t* status,
+                                     int* rows, float* samples, float* costs, long long capacity, long long* total) {
+    return guarded([&] {
+        PLANNER(h);
+        P.solution_paths(nodes, count, lengths, status, rows, samples, costs, capacity, total);
+    });
+}
+
+sbmp_status sbmp_kgmt_trace_rows(sbmp_kgmt* h, const int* rows, long long count, float* steps, uint8_t* status) {
+    return guarded([&] {
+        PLANNER(h);
+        P.trace_rows(rows, count, steps, status);
     });
 }
 

@@ -279,6 +279,44 @@ class KGMT:
                      s.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n))
         return rows, s, c
 
+    def solution_paths(self, nodes) -> dict:
+        """The paths root .. node of many nodes in one device pass (sbmp_kgmt_solution_paths;
+        include/sbmp/tree_paths.h): nodes is (Q,) rows of tree(), -1 for none (a bestRow of
+        query_goals feeds straight in).  Returns lengths (Q,), status (Q,) of SBMP_PATH_* (0 ok,
+        1 none, 2 broken, 3 deep), offsets (Q + 1, int64), and the concatenated rows, samples
+        (total, 7) and costs in solution_path's layout; path i is [offsets[i], offsets[i + 1])."""
+        from .tree_paths import paths_dict
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).ravel()
+        n = nodes.ctypes.data_as(ctypes.c_void_p) if len(nodes) else None
+        return paths_dict(lambda *o: nat.call("sbmp_kgmt_solution_paths", self._h, n, len(nodes), *o), nodes)
+
+    def trace(self, rows=None):
+        """The numDisc Euler states of the edge that ends on each row of `rows` (None: every row
+        of the tree), bit for bit what the planner integrated (sbmp_kgmt_trace_rows).  Returns
+        (steps (count, numDisc, 4) of (x, y, theta, v), a transposed view of the step-major
+        array, status (count,) uint8: SBMP_ROW_FREE, ORPHAN or STALE)."""
+        if rows is None:
+            n = max(1, min(self.result().treeSize, self.M))
+            ptr = None
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+            n = len(rows)
+            ptr = rows.ctypes.data_as(ctypes.c_void_p) if n else None
+        D = self.numDisc_
+        steps = np.zeros((D, max(1, n), 4), dtype=np.float32)
+        status = np.zeros(max(1, n), dtype=np.uint8)
+        nat.call("sbmp_kgmt_trace_rows", self._h, ptr, n, steps.ctypes.data_as(ctypes.c_void_p),
+                 status.ctypes.data_as(ctypes.c_void_p))
+        return steps[:, :n].transpose(1, 0, 2), status[:n]
+
+    def trajectories(self, nodes) -> dict:
+        """solution_paths(nodes) plus `steps` (total, numDisc, 4) and `step_status` (total,): the
+        trace of the concatenated path rows, so path i moves through steps[offsets[i] + 1 :
+        offsets[i + 1]] (the first row of a path is the root, which has no edge)."""
+        out = self.solution_paths(nodes)
+        out["steps"], out["step_status"] = self.trace(out["rows"])
+        return out
+
     def query_goals(self, goals, radius=None, alive: bool = False) -> dict:
         """Goal discs against the tree as it stands (sbmp_kgmt_query_goals; one k_tree_query pass
         per 16 goals): goals is (Q, 2) with one radius for all, or (Q, 3) rows of (x, y, radius).

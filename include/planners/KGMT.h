@@ -140,6 +140,45 @@ public:
         SBMP_CHECK(sbmp_kgmt_query_goals_alive(h_, goals.data(), (int)goals.size(), out.data()));
         return out;
     }
+    // The paths root .. node of many nodes in one device pass (sbmp_kgmt_solution_paths;
+    // sbmp/tree_paths.h): lengths and status (SBMP_PATH_*) per request, node -1 for none; rows,
+    // samples (7 floats per row) and costs hold the paths one behind the other, path i at the sum
+    // of lengths[0 .. i).  Returns the total number of path rows.
+    long long solutionPaths(const std::vector<int>& nodes, std::vector<int>& lengths, std::vector<uint8_t>& status,
+                            std::vector<int>& rows, std::vector<float>& samples, std::vector<float>* costs = nullptr) const {
+        return solutionPathsOf(h_, nodes, lengths, status, rows, samples, costs);
+    }
+    // The numDisc Euler states of the edge that ends on each listed row, bit for bit what the
+    // planner integrated (sbmp_kgmt_trace_rows): steps holds numDisc x rows.size() x 4 floats,
+    // step-major (step j of entry i at 4 * (j * rows.size() + i)); status one SBMP_ROW_* byte each.
+    void traceRows(const std::vector<int>& rows, std::vector<float>& steps, std::vector<uint8_t>& status) const {
+        traceRowsOf(h_, numDisc_, rows, steps, status);
+    }
+    // The two calls on any planner handle (KGMTBatch passes a member's).
+    static long long solutionPathsOf(sbmp_kgmt* h, const std::vector<int>& nodes, std::vector<int>& lengths,
+                                     std::vector<uint8_t>& status, std::vector<int>& rows, std::vector<float>& samples,
+                                     std::vector<float>* costs) {
+        const int count = (int)nodes.size();
+        long long total = 0;
+        lengths.assign(nodes.size(), 0);
+        status.assign(nodes.size(), 0);
+        SBMP_CHECK(sbmp_kgmt_solution_paths(h, nodes.data(), count, lengths.data(), status.data(), nullptr, nullptr,
+                                            nullptr, 0, &total));
+        rows.assign((size_t)total, 0);
+        samples.assign(7 * (size_t)total, 0.0f);
+        if (costs) costs->assign((size_t)total, 0.0f);
+        if (total)
+            SBMP_CHECK(sbmp_kgmt_solution_paths(h, nodes.data(), count, lengths.data(), status.data(), rows.data(),
+                                                samples.data(), costs ? costs->data() : nullptr, total, &total));
+        return total;
+    }
+    static void traceRowsOf(sbmp_kgmt* h, int numDisc, const std::vector<int>& rows, std::vector<float>& steps,
+                            std::vector<uint8_t>& status) {
+        steps.assign(4 * (size_t)numDisc * rows.size(), 0.0f);
+        status.assign(rows.size(), 0);
+        if (!rows.empty())
+            SBMP_CHECK(sbmp_kgmt_trace_rows(h, rows.data(), (long long)rows.size(), steps.data(), status.data()));
+    }
     sbmp_kgmt* handle() const { return h_; }
 
     // Public fields of KGMT.cuh:33-43 that carry meaning outside the class.

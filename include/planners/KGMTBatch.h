@@ -98,6 +98,14 @@ public:
         SBMP_CHECK(sbmp_kgmt_query_goals(member(i), goals.data(), (int)goals.size(), out.data()));
         return out;
     }
+    // Many paths / the Euler steps of listed rows of member i's tree (KGMT::solutionPaths, traceRows).
+    long long solutionPaths(int i, const std::vector<int>& nodes, std::vector<int>& lengths, std::vector<uint8_t>& status,
+                            std::vector<int>& rows, std::vector<float>& samples, std::vector<float>* costs = nullptr) const {
+        return KGMT::solutionPathsOf(member(i), nodes, lengths, status, rows, samples, costs);
+    }
+    void traceRows(int i, const std::vector<int>& rows, std::vector<float>& steps, std::vector<uint8_t>& status) const {
+        KGMT::traceRowsOf(member(i), params_.numDisc, rows, steps, status);
+    }
     sbmp_kgmt_batch* handle() const { return h_; }
 
 private:

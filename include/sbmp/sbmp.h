@@ -291,6 +291,41 @@ sbmp_status sbmp_kgmt_recheck_tree(sbmp_kgmt* h, const float* d_obstacles, int o
 sbmp_status sbmp_kgmt_query_goals_alive(sbmp_kgmt* h, const sbmp_goal_query* goals, int count,
                                         sbmp_goal_answer* out);
 
+/* Many solution paths and the Euler steps of tree rows in one device pass each
+ * (include/sbmp/tree_paths.h states the rule; no reference counterpart).
+ * The path of a node is the chain node, parent[node], ... down to row 0 over the rows [0, R),
+ * R = min(treeSize, maxTreeSize), reported root first; every request gets one status: */
+#define SBMP_PATH_OK 0      /* the chain reaches row 0 within depthBound rows; length = its rows */
+#define SBMP_PATH_NONE 1    /* node == -1 (a bestRow of sbmp_kgmt_query_goals with nothing inside); length 0 */
+#define SBMP_PATH_BROKEN 2  /* a row r > 0 of the chain has no parent in [0, r); length 0 */
+#define SBMP_PATH_DEEP 3    /* more than depthBound rows; length 0 */
+/* nodes: count requests (host).  lengths (ints) and status (bytes): count entries each, may be
+ * NULL.  The paths lie one behind the other in request order, path i at the exclusive sum of
+ * lengths[0 .. i): rows (ints), samples (7 floats per row) and costs in the layout of
+ * sbmp_kgmt_solution_path; each may be NULL, capacity = their length in rows.  *total = the
+ * sum of the lengths, set in every case: with capacity < *total and any of the three given
+ * the call fails with SBMP_ERR_INVALID_ARGUMENT, so a NULL / 0 call returns the size to
+ * allocate.  depthBound is numIterations + 2, as for sbmp_kgmt_solution_path.  Stricter than
+ * that call: it stops at any negative parent, this one reports SBMP_PATH_BROKEN.  A node
+ * < -1 or >= R, nodes NULL with count > 0, count < 0 or total NULL: SBMP_ERR_INVALID_ARGUMENT
+ * before anything is launched.  count == 0 is a no-op (*total = 0).  Before the first begin():
+ * SBMP_ERR_STATE.  The call waits for everything enqueued, runs k_path_walk on the planner's
+ * stream over buffers of its own and only reads the tree: valid after plan() and between
+ * step() calls, on a local shard group (rank 0 answers), a sharded rank (its own replica) and
+ * a batch member; the plan goes on unchanged. */
+sbmp_status sbmp_kgmt_solution_paths(sbmp_kgmt* h, const int* nodes, int count, int* lengths, uint8_t* status,
+                                     int* rows, float* samples, float* costs, long long capacity, long long* total);
+/* The numDisc Euler states of the edge that ends on each listed row: what the planner
+ * integrated and collision-checked, bit for bit.  rows: count row numbers of [0, R) (host), or
+ * NULL for the rows [0, count), count <= R.  steps (host): numDisc x count x 4 floats,
+ * step-major: step j of entry i is the (x, y, theta, v) at steps + 4 * (j * count + i).
+ * status (host, count bytes, may be NULL): SBMP_ROW_FREE (the last step is the stored row bit
+ * for bit; row 0, whose steps all hold the root), SBMP_ROW_ORPHAN (no usable parent: every
+ * step holds the stored row) or SBMP_ROW_STALE.  A listed row outside [0, R), steps NULL or
+ * rows NULL with count > R: SBMP_ERR_INVALID_ARGUMENT.  count == 0 is a no-op; otherwise 0 <
+ * count < 2^31.  State, waiting and handles as sbmp_kgmt_solution_paths (k_tree_trace). */
+sbmp_status sbmp_kgmt_trace_rows(sbmp_kgmt* h, const int* rows, long long count, float* steps, uint8_t* status);
+
 sbmp_status sbmp_kgmt_kernel_stats(sbmp_kgmt* h, sbmp_kernel_stat* out, int capacity, int* count);
 /* The form of the hot path chosen at the last begin() (sbmp_path_info). */
 sbmp_status sbmp_kgmt_path_info(sbmp_kgmt* h, sbmp_path_info* out);
@@ -433,6 +468,38 @@ sbmp_status sbmp_tree_recheck_batch(const sbmp_tree_recheck_args* args, uint8_t*
                                     void* stream /* hipStream_t; NULL: default */);
 sbmp_status sbmp_tree_recheck_batch_host(const sbmp_tree_recheck_args* args, uint8_t* status,
                                          sbmp_tree_recheck* out);
+/* sbmp_tree_paths_batch / sbmp_tree_trace_batch: sbmp_kgmt_solution_paths (k_path_walk) and
+ * sbmp_kgmt_trace_rows (k_tree_trace) over caller rows in the planner's tree layout (state,
+ * ctrl, parent as sbmp_tree_recheck_args, in device memory; 1 <= rows < 2^31).  depthBound:
+ * the most rows a path may hold; <= 0: rows, always sufficient.
+ * sbmp_tree_paths_batch: nodes and every output are host arrays, as sbmp_kgmt_solution_paths.
+ * sbmp_tree_trace_batch: d_rows (count ints, or NULL for the rows [0, count)), d_steps
+ * (numDisc x count x 4 floats, step-major) and d_status (count bytes) are device memory, so the
+ * result can stay on the device; a listed row outside [0, rows) is refused before the launch
+ * (the list is read back for that).  Both wait for the result.  The _host twins take every
+ * array in host memory and apply the literal rule in plain loops (path_rows_host,
+ * trace_rows_host of include/sbmp/tree_paths.h): a second statement of the rule, and they
+ * need no device. */
+typedef struct sbmp_tree_paths_args {
+    const float* state;
+    const float* ctrl;
+    const int* parent;
+    int rows;
+    int depthBound;
+    int agent;                /* SBMP_AGENT_*; the trace only */
+    int numDisc;              /* the trace only */
+    float agentLength;        /* the trace only */
+} sbmp_tree_paths_args;
+sbmp_status sbmp_tree_paths_batch(const sbmp_tree_paths_args* args, const int* nodes, int count, int* lengths,
+                                  uint8_t* status, int* rows, float* samples, float* costs, long long capacity,
+                                  long long* total, void* stream /* hipStream_t; NULL: default */);
+sbmp_status sbmp_tree_paths_batch_host(const sbmp_tree_paths_args* args, const int* nodes, int count, int* lengths,
+                                       uint8_t* status, int* rows, float* samples, float* costs, long long capacity,
+                                       long long* total);
+sbmp_status sbmp_tree_trace_batch(const sbmp_tree_paths_args* args, const int* d_rows, long long count,
+                                  float* d_steps, uint8_t* d_status, void* stream /* hipStream_t; NULL: default */);
+sbmp_status sbmp_tree_trace_batch_host(const sbmp_tree_paths_args* args, const int* rows, long long count,
+                                       float* steps, uint8_t* status);
 
 /* The threshold the kernel compares d2 with (host-only, no device needed): *t = the largest
  * float d2 with sqrtf(d2) < r, found by bisecting the float bit patterns with that rule;
@@ -507,7 +574,8 @@ sbmp_status sbmp_kgmt_batch_enqueue(sbmp_kgmt_batch* h, int iterations);
 sbmp_status sbmp_kgmt_batch_sync(sbmp_kgmt_batch* h);
 sbmp_status sbmp_kgmt_batch_result(sbmp_kgmt_batch* h, int member, sbmp_plan_result* result);
 /* Member i as a planner handle owned by the batch, for every read-only call above
- * (copy_tree, copy_regions, copy_rng, iter_log, solution_path, query_goals, recheck_tree, query_goals_alive, state_hash,
+ * (copy_tree, copy_regions, copy_rng, iter_log, solution_path, solution_paths, trace_rows, query_goals, recheck_tree,
+ * query_goals_alive, state_hash,
  * export_csv, path_info, kernel_stats, ...).  sbmp_kgmt_plan / begin / step / enqueue / destroy on it fail
  * with SBMP_ERR_STATE, sbmp_kgmt_set_iteration_dump with SBMP_ERR_UNSUPPORTED. */
 sbmp_status sbmp_kgmt_batch_member(sbmp_kgmt_batch* h, int i, sbmp_kgmt** borrowed);
