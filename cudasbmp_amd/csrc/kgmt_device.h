@@ -794,24 +794,45 @@ struct ChildCtl {
     float a, steer, dur, dt, tanS;
 };
 
+// The ChildCtl of controls (a | vx, steer | vy, duration, -): as a row stores them
+// (treeCtrl), or as draw_controls has just drawn them.  dt and tan(steer) are functions of
+// the controls and the plan alone, so a replay (k_tree_recheck, k_tree_trace) integrates
+// with the floats the expand step integrated with.
+template <int AGENT>
+__device__ __forceinline__ ChildCtl stored_controls(float4 c, const KgmtDev& d) {
+    ChildCtl ctl;
+    ctl.a = c.x;
+    ctl.steer = c.y;
+    ctl.dur = c.z;
+    ctl.dt = div_or_ieee(c.z, (float)d.numDisc, d.rcpNumDisc);
+    ctl.tanS = (AGENT == 0) ? tan_steer(c.y) : 0.0f;
+    return ctl;
+}
+
 template <int AGENT>
 __device__ __forceinline__ ChildCtl draw_controls(Xorwow& rs, const KgmtDev& d) {
-    ChildCtl c;
+    float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (AGENT == 0) {
-        c.a = __builtin_fmaf(xorwow_uniform(rs), 10.0f, -5.0f);
+        c.x = __builtin_fmaf(xorwow_uniform(rs), 10.0f, -5.0f);
         const float u2 = xorwow_uniform(rs);
-        c.steer = (float)__builtin_fma((double)(u2 * 2.0f), 3.141592653589793, -3.141592653589793);
-        c.dur = __builtin_fmaf(xorwow_uniform(rs), 1.0f, 0.05f);
-        c.dt = div_or_ieee(c.dur, (float)d.numDisc, d.rcpNumDisc);
-        c.tanS = tan_steer(c.steer);
+        c.y = (float)__builtin_fma((double)(u2 * 2.0f), 3.141592653589793, -3.141592653589793);
     } else {
-        c.a = __builtin_fmaf(xorwow_uniform(rs), 2.0f, -1.0f);      // vx
-        c.steer = __builtin_fmaf(xorwow_uniform(rs), 2.0f, -1.0f);  // vy
-        c.dur = __builtin_fmaf(xorwow_uniform(rs), 1.0f, 0.05f);
-        c.dt = div_or_ieee(c.dur, (float)d.numDisc, d.rcpNumDisc);
-        c.tanS = 0.0f;
+        c.x = __builtin_fmaf(xorwow_uniform(rs), 2.0f, -1.0f);   // vx
+        c.y = __builtin_fmaf(xorwow_uniform(rs), 2.0f, -1.0f);   // vy
     }
-    return c;
+    c.z = __builtin_fmaf(xorwow_uniform(rs), 1.0f, 0.05f);
+    return stored_controls<AGENT>(c, d);
+}
+
+// One Euler update of the point's state: x += vx dt, y += vy dt.  point_euler wraps the
+// predicates and the obstacle test round it, point_trace (tree_paths.hip) a store.
+// The car's update is NOT lifted the same way: car_euler's step and car_trace (tree_paths.hip)
+// each hold a copy of it, to be edited together.  Lifted into a function (one with two
+// outputs, and two returning a pair each, by value and by reference), the compiler scheduled
+// the pair FMAs of (x, y) on the other side of the v / L division in every car kernel.
+__device__ __forceinline__ void point_step(float x, float y, float vx, float vy, float dt, float& nx, float& ny) {
+    nx = __builtin_fmaf(vx, dt, x);
+    ny = __builtin_fmaf(vy, dt, y);
 }
 
 // reference statePropagator.cu:5-76 (car).  Same operation sequence as the oracle
@@ -844,6 +865,7 @@ __device__ __forceinline__ bool car_euler(float4 p, const ChildCtl& ctl, const K
     bool alive = true;
     // v / L: one multiply when L is a power of two (invAgentLength != 0), else div_by
     // with an IEEE fallback.  The choice is per plan, so the loop is unswitched on it.
+    // (car_trace of tree_paths.hip holds a copy of this step's state updates: see point_step.)
     auto step = [&](auto invL) {
         if (!alive) return;
         float st, ct;
@@ -909,8 +931,8 @@ __device__ __forceinline__ bool point_euler(float4 p, const ChildCtl& ctl, const
     bool alive = true;
     auto step = [&]() {
         if (!alive) return;
-        const float nx = __builtin_fmaf(vx, dt, x);
-        const float ny = __builtin_fmaf(vy, dt, y);
+        float nx, ny;
+        point_step(x, y, vx, vy, dt, nx, ny);
         const bool oob = cull.bounds && ((seg_min(nx, ny) <= 0.0f) | (nx >= d.width) | (ny >= d.height));
         const float minx = seg_min(x, nx), maxx = seg_max(x, nx);   // see car_euler
         const float miny = seg_min(y, ny), maxy = seg_max(y, ny);

@@ -23,6 +23,7 @@
 
 #include "kgmt_launch.h"
 #include "obstacle_grid.h"
+#include "tree_pass.h"
 
 namespace sbmp {
 
@@ -119,9 +120,7 @@ KgmtPlanner::KgmtPlanner(const sbmp_kgmt_params& p, int nranks, int rank, Exchan
     } else {
         SBMP_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     }
-    // Obstacle-list form of k_expand (diagnostics / A-B): 0 auto, 1 LDS, 2 LDS x4,
-    // 3 registers, 4 grid index at any count, 5 global list without the grid.
-    if (const char* v = getenv("SBMP_EXPAND_VARIANT")) expandVariant_ = std::min(5, std::max(0, atoi(v)));
+    expandVariant_ = expand_variant_from_env();   // obstacle-list form of k_expand (diagnostics / A-B)
 
     const int M = p.maxTreeSize;
     const int nSlots = p.samplesPerIteration > 0 ? std::min(M, p.samplesPerIteration) : M;
@@ -137,7 +136,7 @@ KgmtPlanner::KgmtPlanner(const sbmp_kgmt_params& p, int nranks, int rank, Exchan
     d.nBlocks = slotsPadded_ / kBlock;
     d.batchRule = p.batchRule;
     d.numIterations = p.numIterations;
-    d.numDisc = p.numDisc;
+    set_euler_params(d, p.numDisc, p.agentLength);   // numDisc, agentLength and their reciprocals
     d.N = p.N;
     d.n = p.n;
     d.nR1 = p.N * p.N;
@@ -148,19 +147,11 @@ KgmtPlanner::KgmtPlanner(const sbmp_kgmt_params& p, int nranks, int rank, Exchan
     d.rank = rank;
     d.width = p.width;
     d.height = p.height;
-    d.agentLength = p.agentLength;
-    {   // exact reciprocal only for powers of two (then v * (1/L) == v / L bitwise)
-        int e = 0;
-        const float m = std::frexp(p.agentLength, &e);
-        d.invAgentLength = (m == 0.5f) ? 1.0f / p.agentLength : 0.0f;
-    }
     d.goalThreshold = p.goalThreshold;
     d.R1Size = p.width / (float)p.N;          // KGMT.cu:13
     d.R2Size = p.width / (float)(p.n * p.N);  // KGMT.cu:14
     d.rcpR1Size = markstein_rcp(d.R1Size);
     d.rcpR2Size = markstein_rcp(d.R2Size);
-    d.rcpNumDisc = markstein_rcp((float)p.numDisc);
-    d.rcpAgentLength = markstein_rcp(p.agentLength);
     // dt = duration / numDisc <= 1.05 / numDisc (statePropagator.cu:19-21); 1% above it
     d.reachStep = p.numDisc > 0 ? 1.06f / (float)p.numDisc : 0.0f;
 
@@ -1168,15 +1159,24 @@ unsigned long long KgmtPlanner::state_hash() {
     return h;
 }
 
+// The rows a tree pass covers, [0, min(treeSize, M)): what copy_tree exports, once everything
+// enqueued has finished (result() syncs; the flush pass has inserted the last iteration).
+// wait = false: the state check alone, for a call with nothing to do (it returns 0).
+int KgmtPlanner::settled_rows(bool wait, sbmp_plan_result* r) {
+    if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
+    if (!wait) return 0;
+    sbmp_plan_result mine;
+    if (!r) r = &mine;
+    result(r);
+    return std::min(std::max(r->treeSize, 1), d_.M);
+}
+
 // Goal queries over the rows copy_tree exports (k_tree_query, tree_query.hip): on the
 // planner's stream behind everything enqueued, reading treeState / treeCtrl only.
 void KgmtPlanner::query_goals(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) {
     tree_query_check_goals(goals, count, out);
-    if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
+    const int rows = settled_rows(count > 0);
     if (count == 0) return;
-    sbmp_plan_result r;
-    result(&r);   // syncs (the flush pass has inserted the last iteration)
-    const int rows = std::min(std::max(r.treeSize, 1), d_.M);
     tree_query_device(reinterpret_cast<const float*>(d_.treeState), reinterpret_cast<const float*>(d_.treeCtrl), rows,
                       goals, count, out, stream_);
 }
@@ -1186,10 +1186,8 @@ void KgmtPlanner::query_goals(const sbmp_goal_query* goals, int count, sbmp_goal
 // index stay as begin() left them; the new list lives in the call's own copies.
 void KgmtPlanner::recheck_tree(const float* d_obstacles, int nObs, uint8_t* status, int capacity,
                                sbmp_tree_recheck* out) {
-    if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
     sbmp_plan_result r;
-    result(&r);   // syncs (the flush pass has inserted the last iteration)
-    const int rows = std::min(std::max(r.treeSize, 1), d_.M);
+    const int rows = settled_rows(true, &r);
     *out = sbmp_tree_recheck{rows, 0, 0, 0, 0, 0, -1};
     if (status && capacity < rows)
         throw Error(SBMP_ERR_INVALID_ARGUMENT,
@@ -1210,11 +1208,9 @@ void KgmtPlanner::recheck_tree(const float* d_obstacles, int nObs, uint8_t* stat
 
 void KgmtPlanner::query_goals_alive(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) {
     tree_query_check_goals(goals, count, out);
-    if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
-    if (aliveRows_ < 0) throw Error(SBMP_ERR_STATE, "no recheck_tree since the last begin()");
-    sbmp_plan_result r;
-    result(&r);   // syncs
-    const int rows = std::min(std::max(r.treeSize, 1), d_.M);
+    // checked before the wait; before begin() (aliveRows_ is -1 then too) settled_rows' error is the one
+    if (begun_ && aliveRows_ < 0) throw Error(SBMP_ERR_STATE, "no recheck_tree since the last begin()");
+    const int rows = settled_rows();
     if (rows != aliveRows_)
         throw Error(SBMP_ERR_STATE, "the tree has " + std::to_string(rows) + " rows, the last recheck_tree covered " +
                                         std::to_string(aliveRows_) + ": re-check again");
@@ -1230,11 +1226,8 @@ void KgmtPlanner::solution_paths(const int* nodes, int count, int* lengths, uint
     if (!total) throw Error(SBMP_ERR_INVALID_ARGUMENT, "total must be non-NULL");
     *total = 0;
     if (count < 0 || (count > 0 && !nodes)) throw Error(SBMP_ERR_INVALID_ARGUMENT, "bad node list");
-    if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
+    const int R = settled_rows(count > 0);
     if (count == 0) return;
-    sbmp_plan_result r;
-    result(&r);   // syncs (the flush pass has inserted the last iteration)
-    const int R = std::min(std::max(r.treeSize, 1), d_.M);
     tree_paths_check(nodes, count, R, total);
     // one level per iteration, plus the root: solution_path's bound
     tree_paths_device(d_, R, p_.numIterations + 2, nodes, count, lengths, status, rows, samples, costs, capacity, total,
@@ -1243,11 +1236,8 @@ void KgmtPlanner::solution_paths(const int* nodes, int count, int* lengths, uint
 
 void KgmtPlanner::trace_rows(const int* rows, long long count, float* steps, uint8_t* status) {
     if (count < 0) throw Error(SBMP_ERR_INVALID_ARGUMENT, "count must be >= 0");
-    if (!begun_) throw Error(SBMP_ERR_STATE, "begin() has not been called");
+    const int R = settled_rows(count > 0);
     if (count == 0) return;
-    sbmp_plan_result r;
-    result(&r);   // syncs
-    const int R = std::min(std::max(r.treeSize, 1), d_.M);
     tree_trace_check(rows, count, R, steps);
     tree_trace_to_host(d_, p_.agent, R, rows, count, steps, status, stream_);
 }

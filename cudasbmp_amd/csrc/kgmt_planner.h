@@ -117,12 +117,16 @@ protected:
 void random_tree(int device, int kind, const float* root, int rows, int blocks, int tpb, float* samples,
                  float* kernelMs);
 
+// The passes over a grown tree below share their host-side plumbing: tree_pass.h.
 // Goal queries (tree_query.hip; include/sbmp/tree_query.h): the argument checks of every
 // entry point, k_tree_query over device rows on `stream` (waits for the result), and the
 // literal rule over host rows.
 void tree_query_check_goals(const sbmp_goal_query* goals, int count, const sbmp_goal_answer* out);
 void tree_query_device(const float* d_state, const float* d_ctrl, long long rows, const sbmp_goal_query* goals,
                        int count, sbmp_goal_answer* out, hipStream_t stream);
+// k_tree_query_alive: tree_query_device over the rows whose d_alive byte (tree_recheck_device's mask) is set.
+void tree_query_alive_device(const float* d_state, const float* d_ctrl, const uint8_t* d_alive, long long rows,
+                             const sbmp_goal_query* goals, int count, sbmp_goal_answer* out, hipStream_t stream);
 void tree_query_host(const float* state, const float* ctrl, long long rows, const sbmp_goal_query* goals, int count,
                      sbmp_goal_answer* out);
 sbmp_goal_answer goal_answer_of(unsigned count, unsigned first, unsigned long long best, unsigned long long nearest);
@@ -136,9 +140,6 @@ void tree_recheck_device(const KgmtDev& base, int agent, int variant, int rows, 
                          sbmp_tree_recheck* out, hipStream_t stream);
 void tree_recheck_batch(const sbmp_tree_recheck_args* a, uint8_t* status, sbmp_tree_recheck* out, hipStream_t stream);
 void tree_recheck_batch_host(const sbmp_tree_recheck_args* a, uint8_t* status, sbmp_tree_recheck* out);
-// k_tree_query_alive: tree_query_device over the rows whose d_alive byte is set.
-void tree_query_alive_device(const float* d_state, const float* d_ctrl, const uint8_t* d_alive, long long rows,
-                             const sbmp_goal_query* goals, int count, sbmp_goal_answer* out, hipStream_t stream);
 
 // Paths and traces (tree_paths.hip; include/sbmp/tree_paths.h).  d: the tree pointers and, for
 // the trace, numDisc / agentLength and their reciprocals; `rows` rows.  tree_paths_device: nodes
@@ -348,6 +349,7 @@ private:
     std::vector<void*> allocs_;
     unsigned long long* scratch_ = nullptr;   // 8 device words for small results (state_hash)
     unsigned long long* alloc_scratch_u64();
+    int settled_rows(bool wait = true, sbmp_plan_result* r = nullptr);   // what a tree pass covers; syncs
     uint8_t* alive_ = nullptr;   // recheck_tree's alive mask, one byte per row of [0, aliveRows_)
     int aliveCap_ = 0;
     int aliveRows_ = -1;         // -1: no re-check since the last begin()

@@ -8,13 +8,14 @@
 //                         strictly lower row; no lane waits for another.
 //   k_tree_trace<AGENT>   one lane per listed row (or per row of [0, count)): the row's parent
 //                         first; behind the orphan test the parent's state, the row's controls and
-//                         state; then car_trace / point_trace, the expand step's Euler updates
-//                         (car_euler / point_euler of kgmt_device.h) without the cull, the
-//                         predicates and the exec masking.  Every step is one 16-byte store per lane,
+//                         state (stored_controls); then car_trace / point_trace, the expand step's
+//                         Euler updates (car_euler / point_euler of kgmt_device.h) without the cull,
+//                         the predicates and the exec masking.  Every step is one 16-byte store per lane,
 //                         step-major, consecutive lanes on consecutive addresses; one status byte.
 //   sbmp_tree_paths_batch / _host, sbmp_tree_trace_batch / _host, and what
 //   sbmp_kgmt_solution_paths / sbmp_kgmt_trace_rows run (KgmtPlanner::solution_paths, trace_rows)
 // Stream order between the launches is the only ordering; every output element has one writer.
+// The trace's grid, the buffers and the read-backs are tree_pass.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +28,7 @@
 #include "sbmp/sbmp.h"
 #include "sbmp/tree_paths.h"
 #include "sbmp/tree_recheck.h"
+#include "tree_pass.h"
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -76,8 +78,10 @@ __global__ __launch_bounds__(kPathsBlock) void k_path_walk(const float4* __restr
 
 // car_euler's state updates (kgmt_device.h) and nothing else: the same sincos_pred, the same
 // v / L switch (one multiply for a power-of-two L, else div_by with the IEEE fallback), the same
-// packed pair FMAs, so every step is the float the planner integrated.  out: the lane's first
-// step; the next step lies `stride` float4s on.
+// packed pair FMAs, so every step is the float the planner integrated.  A hand copy, to be
+// edited with car_euler's step: sharing one function moved every car kernel's code (see
+// point_step, kgmt_device.h).  out: the lane's first step; the next step lies `stride`
+// float4s on.
 __device__ __forceinline__ float4 car_trace(float4 p, const ChildCtl& ctl, const KgmtDev& d, float4* out, size_t stride) {
     const float a = ctl.a, dt = ctl.dt, tan_steering = ctl.tanS;
     sbmp_f32x2 xy = {p.x, p.y}, tv = {p.z, p.w};
@@ -111,14 +115,12 @@ __device__ __forceinline__ float4 car_trace(float4 p, const ChildCtl& ctl, const
     return make_float4(xy.x, xy.y, tv.x, tv.y);
 }
 
-// point_euler's updates likewise.
+// point_euler's loop likewise: point_step and a store.
 __device__ __forceinline__ float4 point_trace(float4 p, const ChildCtl& ctl, const KgmtDev& d, float4* out, size_t stride) {
-    const float vx = ctl.a, vy = ctl.steer, dt = ctl.dt;
     float x = p.x, y = p.y;
     const int nSteps = __builtin_amdgcn_readfirstlane(d.numDisc);
     for (int i = 0; i < nSteps; ++i) {
-        x = __builtin_fmaf(vx, dt, x);
-        y = __builtin_fmaf(vy, dt, y);
+        point_step(x, y, ctl.a, ctl.steer, ctl.dt, x, y);
         *out = make_float4(x, y, 0.0f, 0.0f);
         out += stride;
     }
@@ -151,44 +153,13 @@ __global__ __launch_bounds__(kPathsBlock) void k_tree_trace(KgmtDev d, const int
             st = r == 0 ? SBMP_ROW_FREE : SBMP_ROW_ORPHAN;
         } else {
             const float4 p = tState[parent];
-            const float4 c = tCtrl[r];
-            ChildCtl ctl;   // draw_controls' tail, with the controls read instead of drawn
-            ctl.a = c.x;
-            ctl.steer = c.y;
-            ctl.dur = c.z;
-            ctl.dt = div_or_ieee(c.z, (float)d.numDisc, d.rcpNumDisc);
-            ctl.tanS = (AGENT == 0) ? tan_steer(c.y) : 0.0f;
+            const ChildCtl ctl = stored_controls<AGENT>(tCtrl[r], d);
             const float4 e = (AGENT == 0) ? car_trace(p, ctl, d, out, plane) : point_trace(p, ctl, d, out, plane);
             st = recheck_same_state(e.x, e.y, e.z, e.w, me.x, me.y, me.z, me.w) ? SBMP_ROW_FREE : SBMP_ROW_STALE;
         }
         status[i] = st;
     }
 }
-
-int trace_grid(const void* fn, long long count) {
-    int dev = 0, perCU = 0, cus = 0;
-    SBMP_HIP(hipGetDevice(&dev));
-    SBMP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, fn, kPathsBlock, 0));
-    SBMP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (perCU < 1 || cus < 1) throw Error(SBMP_ERR_HIP, "k_tree_trace: the occupancy query gave no resident workgroup");
-    const long long need = (count + kPathsBlock - 1) / kPathsBlock;
-    return (int)std::min<long long>((long long)std::min(perCU, kTraceGroupsPerCU) * cus, std::max(need, 1ll));
-}
-
-// Device buffers of one call, freed with it.
-struct DevBufs {
-    std::vector<void*> p;
-    ~DevBufs() {
-        for (void* q : p) (void)hipFree(q);
-    }
-    template <typename T>
-    T* alloc(size_t n) {
-        void* q = nullptr;
-        SBMP_HIP(hipMalloc(&q, sizeof(T) * std::max<size_t>(n, 1)));
-        p.push_back(q);
-        return static_cast<T*>(q);
-    }
-};
 
 void check_paths_args(const sbmp_tree_paths_args* a) {
     if (!a) throw Error(SBMP_ERR_INVALID_ARGUMENT, "args must be non-NULL");
@@ -204,15 +175,10 @@ void check_trace_args(const sbmp_tree_paths_args* a) {
 
 int bound_of(const sbmp_tree_paths_args* a) { return a->depthBound > 0 ? a->depthBound : a->rows; }
 
-// what the kernels read of a plan (KgmtPlanner's constructor sets the same fields)
+// what the kernels read of a plan
 KgmtDev dev_of(const sbmp_tree_paths_args* a) {
     KgmtDev d{};
-    d.numDisc = std::max(a->numDisc, 1);
-    d.agentLength = a->agentLength;
-    int ex = 0;
-    d.invAgentLength = (std::frexp(a->agentLength, &ex) == 0.5f) ? 1.0f / a->agentLength : 0.0f;
-    d.rcpNumDisc = markstein_rcp((float)d.numDisc);
-    d.rcpAgentLength = markstein_rcp(a->agentLength);
+    set_euler_params(d, std::max(a->numDisc, 1), a->agentLength);
     d.treeState = reinterpret_cast<float4*>(const_cast<float*>(a->state));
     d.treeCtrl = reinterpret_cast<float4*>(const_cast<float*>(a->ctrl));
     d.treeParent = const_cast<int*>(a->parent);
@@ -234,8 +200,7 @@ void tree_paths_device(const KgmtDev& d, int rows, int depthBound, const int* no
     if (count == 0) return;
     (void)rows;
     DevBufs w;
-    hipError_t e = hipSuccess;
-    try {
+    drained_on_throw(stream, [&] {
         int* dNodes = w.alloc<int>(count);
         int* dLen = w.alloc<int>(count);
         uint8_t* dStatus = w.alloc<uint8_t>(count);
@@ -246,11 +211,7 @@ void tree_paths_device(const KgmtDev& d, int rows, int depthBound, const int* no
                            (const float4*)d.treeCtrl, (const int*)d.treeParent, depthBound, (const int*)dNodes, count,
                            dLen, dStatus, (const long long*)nullptr, (int*)nullptr, (float*)nullptr, (float*)nullptr);
         SBMP_HIP(hipGetLastError());
-        e = hipMemcpyAsync(hLen.data(), dLen, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, stream);
-        if (status && e == hipSuccess) e = hipMemcpyAsync(status, dStatus, (size_t)count, hipMemcpyDeviceToHost, stream);
-        hipError_t e2 = hipStreamSynchronize(stream);
-        if (e == hipSuccess) e = e2;
-        SBMP_HIP(e);
+        read_back(stream, {{hLen.data(), dLen, sizeof(int) * (size_t)count}, {status, dStatus, (size_t)count}});
         std::vector<long long> off(count);
         long long sum = 0;
         for (int i = 0; i < count; ++i) {
@@ -273,18 +234,10 @@ void tree_paths_device(const KgmtDev& d, int rows, int depthBound, const int* no
                            (const float4*)d.treeCtrl, (const int*)d.treeParent, depthBound, (const int*)dNodes, count,
                            dLen, dStatus, (const long long*)dOff, dRows, dSamples, dCosts);
         SBMP_HIP(hipGetLastError());
-        if (outRows) e = hipMemcpyAsync(outRows, dRows, sizeof(int) * (size_t)sum, hipMemcpyDeviceToHost, stream);
-        if (samples && e == hipSuccess)
-            e = hipMemcpyAsync(samples, dSamples, sizeof(float) * 7 * (size_t)sum, hipMemcpyDeviceToHost, stream);
-        if (costs && e == hipSuccess)
-            e = hipMemcpyAsync(costs, dCosts, sizeof(float) * (size_t)sum, hipMemcpyDeviceToHost, stream);
-        e2 = hipStreamSynchronize(stream);
-        if (e == hipSuccess) e = e2;
-    } catch (...) {
-        (void)hipStreamSynchronize(stream);   // nothing in flight when the buffers are freed
-        throw;
-    }
-    SBMP_HIP(e);
+        read_back(stream, {{outRows, dRows, sizeof(int) * (size_t)sum},
+                           {samples, dSamples, sizeof(float) * 7 * (size_t)sum},
+                           {costs, dCosts, sizeof(float) * (size_t)sum}});
+    });
 }
 
 void tree_trace_check(const int* list, long long count, int rows, const float* steps) {
@@ -305,7 +258,7 @@ void tree_trace_device(const KgmtDev& d, int agent, int rows, const int* d_list,
     (void)rows;
     using Fn = decltype(&k_tree_trace<0>);
     const Fn fn = (agent == SBMP_AGENT_POINT) ? k_tree_trace<1> : k_tree_trace<0>;
-    const int grid = trace_grid(reinterpret_cast<const void*>(fn), count);
+    const int grid = resident_grid(fn, kPathsBlock, 0, kTraceGroupsPerCU, count, "k_tree_trace");
     hipLaunchKernelGGL(fn, dim3(grid), dim3(kPathsBlock), 0, stream, d, d_list, (unsigned)count,
                        reinterpret_cast<float4*>(d_steps), d_status);
     SBMP_HIP(hipGetLastError());
@@ -315,23 +268,15 @@ void tree_trace_device(const KgmtDev& d, int agent, int rows, const int* d_list,
 void tree_trace_to_host(const KgmtDev& d, int agent, int rows, const int* list, long long count, float* steps,
                         uint8_t* status, hipStream_t stream) {
     DevBufs w;
-    hipError_t e = hipSuccess;
-    try {
+    drained_on_throw(stream, [&] {
         const size_t floats = 4 * (size_t)d.numDisc * (size_t)count;
         int* dList = list ? w.alloc<int>((size_t)count) : nullptr;
         float* dSteps = w.alloc<float>(floats);
         uint8_t* dStatus = w.alloc<uint8_t>((size_t)count);
         if (list) SBMP_HIP(hipMemcpyAsync(dList, list, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, stream));
         tree_trace_device(d, agent, rows, dList, count, dSteps, dStatus, stream);
-        e = hipMemcpyAsync(steps, dSteps, sizeof(float) * floats, hipMemcpyDeviceToHost, stream);
-        if (status && e == hipSuccess) e = hipMemcpyAsync(status, dStatus, (size_t)count, hipMemcpyDeviceToHost, stream);
-        const hipError_t e2 = hipStreamSynchronize(stream);
-        if (e == hipSuccess) e = e2;
-    } catch (...) {
-        (void)hipStreamSynchronize(stream);
-        throw;
-    }
-    SBMP_HIP(e);
+        read_back(stream, {{steps, dSteps, sizeof(float) * floats}, {status, dStatus, (size_t)count}});
+    });
 }
 
 void tree_paths_batch(const sbmp_tree_paths_args* a, const int* nodes, int count, int* lengths, uint8_t* status,

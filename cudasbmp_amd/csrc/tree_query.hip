@@ -2,13 +2,18 @@
 // rule): for each goal disc, how many rows lie inside, the lowest of them,
 // the cheapest of them, and the row nearest to the centre.
 //   k_tree_query             one streaming pass over the rows for a tile of up to 16 goals
+//   k_tree_query_alive       the same query over the rows a re-check (tree_recheck.hip) left
+//                            alive: one masked row per lane, tiles of 8, 4 and 1
 //   sbmp_tree_query_batch    the kernel over caller rows (tree_query_device)
 //   sbmp_tree_query_batch_host   a plain host loop with the literal rule (tree_query_host)
 //   sbmp_kgmt_query_goals    the kernel over a planner's tree (KgmtPlanner::query_goals)
-// The kernel reads treeState once, 16 B per row; a row's cost (treeCtrl.w) is read only by
+//   sbmp_kgmt_query_goals_alive  the masked kernel (KgmtPlanner::query_goals_alive)
+// The kernels read treeState once, 16 B per row; a row's cost (treeCtrl.w) is read only by
 // a lane whose row is inside some disc.  Every reduction is an integer add or an unsigned
 // minimum (of a row, or of goal_key = value bits << 32 | row), so the answer does not
 // depend on the order rows arrive in: it is the same bits on every run, whatever the grid.
+// The two kernels share the tile, the init kernel and the host path (goal_query_device); the
+// grid, the buffers and the read-back are tree_pass.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +24,7 @@
 #include "kgmt_planner.h"
 #include "sbmp/sbmp.h"
 #include "sbmp/tree_query.h"
+#include "tree_pass.h"
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -39,7 +45,7 @@ constexpr int kQueryGroupsPerCU = 8;
 // (kernel-argument loads are scalar), and the loops over them unroll.
 template <int NG>
 struct QueryTile {
-    float gx[NG], gy[NG], t[NG];
+    float gx[NG], gy[NG], t[NG];   // t: goal_radius_threshold(radius); -1 for padding
 };
 
 __global__ void k_tree_query_init(QueryAcc* acc, int count) {
@@ -154,7 +160,9 @@ __global__ __launch_bounds__(kQueryBlock) void k_tree_query(const float4* __rest
         if (c < full) query_rows<NG, false>(state, ctrl, rows, base, q, nb, nr, sGoal, sCount, sFirst, sBest);
         else query_rows<NG, true>(state, ctrl, rows, base, q, nb, nr, sGoal, sCount, sFirst, sBest);
     }
-    // nearest: lanes -> wave -> workgroup
+    // nearest: lanes -> wave -> workgroup.  (k_tree_query_alive ends with a copy of these 20
+    // lines, to be edited together: as one function that both kernels call, in four shapes, the
+    // compiler moved k_tree_query<1>'s row loop, and in two of them every instantiation's.)
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         unsigned long long key = ((unsigned long long)nb[g] << 32) | nr[g];   // kNoGoalKey for a lane without rows
@@ -177,26 +185,86 @@ __global__ __launch_bounds__(kQueryBlock) void k_tree_query(const float4* __rest
     }
 }
 
+// The masked query: a row whose alive byte is 0 is skipped as if the tree did not hold it.
+// A kernel of its own, shaped differently on purpose (one row per lane and sweep, no slack
+// test: the mask already thins the rows), so that no k_tree_query instantiation changes.
+template <int NG>
+__global__ __launch_bounds__(kQueryBlock) void k_tree_query_alive(const float4* __restrict__ state,
+                                                                  const float4* __restrict__ ctrl,
+                                                                  const uint8_t* __restrict__ alive, long long rows,
+                                                                  QueryTile<NG> q, int n, QueryAcc* __restrict__ acc) {
+    __shared__ unsigned sCount[NG], sFirst[NG];
+    __shared__ unsigned long long sBest[NG], sNear[NG];
+    if (threadIdx.x < NG) {
+        sCount[threadIdx.x] = 0u;
+        sFirst[threadIdx.x] = ~0u;
+        sBest[threadIdx.x] = kNoGoalKey;
+        sNear[threadIdx.x] = kNoGoalKey;
+    }
+    __syncthreads();
+    uint32_t nb[NG], nr[NG];   // the lane's lowest d2 (as bits: d2 >= 0) per goal and its row
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        nb[g] = ~0u;
+        nr[g] = ~0u;
+    }
+    const long long stride = (long long)gridDim.x * kQueryBlock;
+    for (long long row = (long long)blockIdx.x * kQueryBlock + threadIdx.x; row < rows; row += stride) {
+        if (!alive[row]) continue;
+        const float4 s = state[row];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const float d2 = goal_d2(s.x, s.y, q.gx[g], q.gy[g]);
+            const uint32_t b = __float_as_uint(d2);
+            if (b < nb[g]) {   // a lane meets its rows in ascending order: the lowest row of equal d2 stays
+                nb[g] = b;
+                nr[g] = (uint32_t)row;
+            }
+            if (d2 <= q.t[g]) {
+                atomicAdd(&sCount[g], 1u);
+                atomicMin(&sFirst[g], (unsigned)row);
+                atomicMin(&sBest[g], goal_key(ctrl[row].w, (uint32_t)row));
+            }
+        }
+    }
+    // k_tree_query's epilogue (see there)
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        unsigned long long key = ((unsigned long long)nb[g] << 32) | nr[g];   // kNoGoalKey for a lane without rows
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long other = __shfl_xor(key, off, 64);
+            key = other < key ? other : key;
+        }
+        if ((threadIdx.x & 63) == 0 && key != kNoGoalKey) atomicMin(&sNear[g], key);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < n) {
+        const int g = threadIdx.x;
+        if (sCount[g]) {
+            atomicAdd(&acc[g].count, sCount[g]);
+            atomicMin(&acc[g].first, sFirst[g]);
+            atomicMin(&acc[g].best, sBest[g]);
+        }
+        if (sNear[g] != kNoGoalKey) atomicMin(&acc[g].nearest, sNear[g]);
+    }
+}
+
 // Workgroups of k_tree_query<NG> the device holds at once, at most kQueryGroupsPerCU per CU.
+// Cached per device: a single-tile query is short enough for the occupancy query to show.
 template <int NG>
 int query_resident_groups() {
     static int cached[64] = {0};
     int dev = 0;
     SBMP_HIP(hipGetDevice(&dev));
     if (dev >= 0 && dev < 64 && cached[dev]) return cached[dev];
-    int perCU = 0, cus = 0;
-    SBMP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_tree_query<NG>, kQueryBlock, 0));
-    SBMP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (perCU < 1 || cus < 1) throw Error(SBMP_ERR_HIP, "k_tree_query: the occupancy query gave no resident workgroup");
-    const int groups = std::min(perCU, kQueryGroupsPerCU) * cus;
+    const int groups = resident_grid(k_tree_query<NG>, kQueryBlock, 0, kQueryGroupsPerCU, kWholeDevice, "k_tree_query");
     if (dev >= 0 && dev < 64) cached[dev] = groups;
     return groups;
 }
 
-// One pass for the goals [first, first + n) of xyt (n <= NG).
+// The goals [first, first + n) of xyt (n <= NG) as a tile; the rest is padding.
 template <int NG>
-void launch_query_tile(const float4* state, const float4* ctrl, long long rows, const float* xyt, int first, int n,
-                       QueryAcc* acc, hipStream_t s) {
+QueryTile<NG> fill_query_tile(const float* xyt, int first, int n) {
     QueryTile<NG> q;
     for (int g = 0; g < NG; ++g) {
         const bool real = g < n;
@@ -204,14 +272,70 @@ void launch_query_tile(const float4* state, const float4* ctrl, long long rows, 
         q.gy[g] = real ? xyt[3 * (size_t)(first + g) + 1] : 0.0f;
         q.t[g] = real ? xyt[3 * (size_t)(first + g) + 2] : -1.0f;
     }
-    const long long chunks = (rows + kQueryChunk - 1) / kQueryChunk;
-    const int grid = (int)std::min<long long>(query_resident_groups<NG>(), chunks);
-    hipLaunchKernelGGL(k_tree_query<NG>, dim3(grid), dim3(kQueryBlock), 0, s, state, ctrl, rows, q, n, acc + first);
+    return q;
 }
 
-void check_query_rows(const void* state, const void* ctrl, long long rows) {
-    if (!state || !ctrl) throw Error(SBMP_ERR_INVALID_ARGUMENT, "state and ctrl must be non-NULL");
+// One pass for the goals [first, first + n) of xyt (n <= NG).
+template <int NG>
+void launch_query_tile(const float4* state, const float4* ctrl, long long rows, const float* xyt, int first, int n,
+                       QueryAcc* acc, hipStream_t s) {
+    const long long chunks = (rows + kQueryChunk - 1) / kQueryChunk;
+    const int grid = (int)std::min<long long>(query_resident_groups<NG>(), chunks);
+    hipLaunchKernelGGL(k_tree_query<NG>, dim3(grid), dim3(kQueryBlock), 0, s, state, ctrl, rows,
+                       fill_query_tile<NG>(xyt, first, n), n, acc + first);
+}
+
+template <int NG>
+void launch_alive_tile(const float4* state, const float4* ctrl, const uint8_t* alive, long long rows, const float* xyt,
+                       int first, int n, QueryAcc* acc, hipStream_t s) {
+    const int grid = resident_grid(k_tree_query_alive<NG>, kQueryBlock, 0, kQueryGroupsPerCU, rows, "k_tree_query_alive");
+    hipLaunchKernelGGL(k_tree_query_alive<NG>, dim3(grid), dim3(kQueryBlock), 0, s, state, ctrl, alive, rows,
+                       fill_query_tile<NG>(xyt, first, n), n, acc + first);
+}
+
+void launch_query_init(QueryAcc* acc, int count, hipStream_t s) {
+    hipLaunchKernelGGL(k_tree_query_init, dim3((count + 255) / 256), dim3(256), 0, s, acc, count);
+}
+
+// The masked query's launches: tiles of 8 (its centres and thresholds still fit the SGPRs), 4, 1.
+void launch_tree_query_alive(const float4* state, const float4* ctrl, const uint8_t* alive, long long rows,
+                             const float* xyt, int count, QueryAcc* acc, hipStream_t s) {
+    launch_query_init(acc, count, s);
+    for (int first = 0; first < count;) {
+        const int left = count - first;
+        const int n = left >= 8 ? 8 : left >= 4 ? 4 : 1;
+        if (n == 8) launch_alive_tile<8>(state, ctrl, alive, rows, xyt, first, n, acc, s);
+        else if (n == 4) launch_alive_tile<4>(state, ctrl, alive, rows, xyt, first, n, acc, s);
+        else launch_alive_tile<1>(state, ctrl, alive, rows, xyt, first, n, acc, s);
+        first += n;
+    }
+    SBMP_HIP(hipGetLastError());
+}
+
+void check_query_rows(long long rows) {
     if (rows < 1 || rows > 0x7fffffffll) throw Error(SBMP_ERR_INVALID_ARGUMENT, "rows must be in [1, 2^31)");
+}
+
+// The host path of both queries: the goals' thresholds, the accumulators (the call's own), the
+// launches (launch(xyt, acc): the init kernel and the tiles, on `stream`), the keys back and
+// into answers.  Waits for the result.
+template <class Launch>
+void goal_query_device(const sbmp_goal_query* goals, int count, sbmp_goal_answer* out, hipStream_t stream,
+                       Launch launch) {
+    std::vector<float> xyt(3 * (size_t)count);
+    for (int i = 0; i < count; ++i) {
+        xyt[3 * (size_t)i] = goals[i].x;
+        xyt[3 * (size_t)i + 1] = goals[i].y;
+        xyt[3 * (size_t)i + 2] = goal_radius_threshold(goals[i].radius);
+    }
+    std::vector<QueryAcc> host(count);
+    DevBufs w;
+    QueryAcc* acc = w.alloc<QueryAcc>(count);
+    drained_on_throw(stream, [&] {
+        launch(xyt.data(), acc);
+        read_back(stream, {{host.data(), acc, sizeof(QueryAcc) * (size_t)count}});
+    });
+    for (int i = 0; i < count; ++i) out[i] = goal_answer_of(host[i].count, host[i].first, host[i].best, host[i].nearest);
 }
 
 }  // namespace
@@ -230,7 +354,7 @@ sbmp_goal_answer goal_answer_of(unsigned count, unsigned first, unsigned long lo
 void launch_tree_query(const float4* state, const float4* ctrl, long long rows, const float* goalsXYT, int count,
                        QueryAcc* acc, hipStream_t s) {
     if (count <= 0) return;
-    hipLaunchKernelGGL(k_tree_query_init, dim3((count + 255) / 256), dim3(256), 0, s, acc, count);
+    launch_query_init(acc, count, s);
     // whole tiles of kQueryTile goals, then the rest in the smallest tile that holds it
     for (int first = 0; first < count;) {
         const int left = count - first;
@@ -258,44 +382,36 @@ void tree_query_check_goals(const sbmp_goal_query* goals, int count, const sbmp_
             throw Error(SBMP_ERR_INVALID_ARGUMENT, "goal " + std::to_string(i) + " has a non-finite coordinate");
 }
 
-// The goals' thresholds on the host, the kernel on `stream`, the keys back and into answers.
-// Waits for the result.
 void tree_query_device(const float* d_state, const float* d_ctrl, long long rows, const sbmp_goal_query* goals,
                        int count, sbmp_goal_answer* out, hipStream_t stream) {
     tree_query_check_goals(goals, count, out);
-    check_query_rows(d_state, d_ctrl, rows);
+    if (!d_state || !d_ctrl) throw Error(SBMP_ERR_INVALID_ARGUMENT, "state and ctrl must be non-NULL");
+    check_query_rows(rows);
     if (count == 0) return;
-    std::vector<float> xyt(3 * (size_t)count);
-    for (int i = 0; i < count; ++i) {
-        xyt[3 * (size_t)i] = goals[i].x;
-        xyt[3 * (size_t)i + 1] = goals[i].y;
-        xyt[3 * (size_t)i + 2] = goal_radius_threshold(goals[i].radius);
-    }
-    std::vector<QueryAcc> host(count);
-    QueryAcc* acc = nullptr;
-    SBMP_HIP(hipMalloc(reinterpret_cast<void**>(&acc), sizeof(QueryAcc) * (size_t)count));
-    hipError_t e = hipSuccess;
-    try {
-        launch_tree_query(reinterpret_cast<const float4*>(d_state), reinterpret_cast<const float4*>(d_ctrl), rows,
-                          xyt.data(), count, acc, stream);
-        e = hipMemcpyAsync(host.data(), acc, sizeof(QueryAcc) * (size_t)count, hipMemcpyDeviceToHost, stream);
-        const hipError_t e2 = hipStreamSynchronize(stream);
-        if (e == hipSuccess) e = e2;
-    } catch (...) {
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(acc);
-        throw;
-    }
-    (void)hipFree(acc);
-    SBMP_HIP(e);
-    for (int i = 0; i < count; ++i) out[i] = goal_answer_of(host[i].count, host[i].first, host[i].best, host[i].nearest);
+    goal_query_device(goals, count, out, stream, [&](const float* xyt, QueryAcc* acc) {
+        launch_tree_query(reinterpret_cast<const float4*>(d_state), reinterpret_cast<const float4*>(d_ctrl), rows, xyt,
+                          count, acc, stream);
+    });
+}
+
+void tree_query_alive_device(const float* d_state, const float* d_ctrl, const uint8_t* d_alive, long long rows,
+                             const sbmp_goal_query* goals, int count, sbmp_goal_answer* out, hipStream_t stream) {
+    tree_query_check_goals(goals, count, out);
+    if (!d_state || !d_ctrl || !d_alive) throw Error(SBMP_ERR_INVALID_ARGUMENT, "state, ctrl and alive must be non-NULL");
+    check_query_rows(rows);
+    if (count == 0) return;
+    goal_query_device(goals, count, out, stream, [&](const float* xyt, QueryAcc* acc) {
+        launch_tree_query_alive(reinterpret_cast<const float4*>(d_state), reinterpret_cast<const float4*>(d_ctrl),
+                                d_alive, rows, xyt, count, acc, stream);
+    });
 }
 
 // The literal rule, row by row (no threshold): what the kernel must reproduce.
 void tree_query_host(const float* state, const float* ctrl, long long rows, const sbmp_goal_query* goals, int count,
                      sbmp_goal_answer* out) {
     tree_query_check_goals(goals, count, out);
-    check_query_rows(state, ctrl, rows);
+    if (!state || !ctrl) throw Error(SBMP_ERR_INVALID_ARGUMENT, "state and ctrl must be non-NULL");
+    check_query_rows(rows);
     for (int i = 0; i < count; ++i) {
         unsigned n = 0u, first = ~0u;
         unsigned long long best = kNoGoalKey, nearest = kNoGoalKey;

@@ -9,8 +9,9 @@
 //                               dead[anc[r]], anc'[r] = anc[anc[r]].  The status bytes are the
 //                               first dead array (FREE is 0).  The last pass writes the exported
 //                               bytes, the alive mask and the summary.
-//   k_tree_query_alive<NG>      the goal query of tree_query.hip over the alive rows only
-//   sbmp_tree_recheck_batch / _host, sbmp_kgmt_recheck_tree, sbmp_kgmt_query_goals_alive
+//   sbmp_tree_recheck_batch / _host, sbmp_kgmt_recheck_tree
+// The goal query over the alive mask (k_tree_query_alive) lives in tree_query.hip, beside the
+// query it masks; the grids, the buffers and the read-back are tree_pass.h's.
 // No workgroup waits for another inside a kernel: stream order between the launches is the
 // only ordering.  Every pass reads one buffer pair and writes the other, and the summary is
 // integer adds and one unsigned minimum, so the bytes and the counts do not depend on the
@@ -19,7 +20,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -27,8 +27,8 @@
 #include "kgmt_planner.h"
 #include "obstacle_grid.h"
 #include "sbmp/sbmp.h"
-#include "sbmp/tree_query.h"
 #include "sbmp/tree_recheck.h"
+#include "tree_pass.h"
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -90,12 +90,7 @@ __global__ __launch_bounds__(kRecheckBlock) void k_tree_recheck(KgmtDev d, unsig
                 const float4 p = tState[parent];
                 const float4 c = tCtrl[r];
                 const float4 me = tState[r];
-                ChildCtl ctl;   // draw_controls' tail, with the controls read instead of drawn
-                ctl.a = c.x;
-                ctl.steer = c.y;
-                ctl.dur = c.z;
-                ctl.dt = div_or_ieee(c.z, (float)d.numDisc, d.rcpNumDisc);
-                ctl.tanS = (AGENT == 0) ? tan_steer(c.y) : 0.0f;
+                const ChildCtl ctl = stored_controls<AGENT>(c, d);
                 ChildOut out;
                 const bool valid = (AGENT == 0) ? car_euler<OBS>(p, ctl, d, obs, out) : point_euler<OBS>(p, ctl, d, obs, out);
                 st = recheck_replayed_status(valid, recheck_same_state(out.state.x, out.state.y, out.state.z,
@@ -161,172 +156,68 @@ __global__ __launch_bounds__(kRecheckBlock) void k_tree_alive(const int* __restr
     }
 }
 
-// ---------------------------------------------------------------- masked goal query
-// A kernel of its own, so that no k_tree_query instantiation changes.  A row that is not
-// alive is skipped as if the tree did not hold it; the reductions are k_tree_query's
-// (integer adds, unsigned minima of goal_key), so the answers are the same bits on every run.
-template <int NG>
-struct AliveTile {
-    float gx[NG], gy[NG], t[NG];   // t: goal_radius_threshold(radius); -1 for padding
-};
-
-__global__ void k_tree_query_alive_init(QueryAcc* acc, int count) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) {
-        acc[i].best = kNoGoalKey;
-        acc[i].nearest = kNoGoalKey;
-        acc[i].count = 0u;
-        acc[i].first = ~0u;
-    }
-}
-
-template <int NG>
-__global__ __launch_bounds__(kRecheckBlock) void k_tree_query_alive(const float4* __restrict__ state,
-                                                                    const float4* __restrict__ ctrl,
-                                                                    const uint8_t* __restrict__ alive, long long rows,
-                                                                    AliveTile<NG> q, int n, QueryAcc* __restrict__ acc) {
-    __shared__ unsigned sCount[NG], sFirst[NG];
-    __shared__ unsigned long long sBest[NG], sNear[NG];
-    if (threadIdx.x < NG) {
-        sCount[threadIdx.x] = 0u;
-        sFirst[threadIdx.x] = ~0u;
-        sBest[threadIdx.x] = kNoGoalKey;
-        sNear[threadIdx.x] = kNoGoalKey;
-    }
-    __syncthreads();
-    uint32_t nb[NG], nr[NG];   // the lane's lowest d2 (as bits: d2 >= 0) per goal and its row
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        nb[g] = ~0u;
-        nr[g] = ~0u;
-    }
-    const long long stride = (long long)gridDim.x * kRecheckBlock;
-    for (long long row = (long long)blockIdx.x * kRecheckBlock + threadIdx.x; row < rows; row += stride) {
-        if (!alive[row]) continue;
-        const float4 s = state[row];
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const float d2 = goal_d2(s.x, s.y, q.gx[g], q.gy[g]);
-            const uint32_t b = __float_as_uint(d2);
-            if (b < nb[g]) {   // a lane meets its rows in ascending order: the lowest row of equal d2 stays
-                nb[g] = b;
-                nr[g] = (uint32_t)row;
-            }
-            if (d2 <= q.t[g]) {
-                atomicAdd(&sCount[g], 1u);
-                atomicMin(&sFirst[g], (unsigned)row);
-                atomicMin(&sBest[g], goal_key(ctrl[row].w, (uint32_t)row));
-            }
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        unsigned long long key = ((unsigned long long)nb[g] << 32) | nr[g];   // kNoGoalKey for a lane without rows
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long other = __shfl_xor(key, off, 64);
-            key = other < key ? other : key;
-        }
-        if ((threadIdx.x & 63) == 0 && key != kNoGoalKey) atomicMin(&sNear[g], key);
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < n) {
-        const int g = threadIdx.x;
-        if (sCount[g]) {
-            atomicAdd(&acc[g].count, sCount[g]);
-            atomicMin(&acc[g].first, sFirst[g]);
-            atomicMin(&acc[g].best, sBest[g]);
-        }
-        if (sNear[g] != kNoGoalKey) atomicMin(&acc[g].nearest, sNear[g]);
-    }
-}
-
 // ---------------------------------------------------------------- host side
-// Workgroups of kRecheckBlock lanes for `rows` rows: what the device holds at once of fn (at
-// most kRecheckGroupsPerCU per CU), and no more than the rows need.
-int recheck_grid(const void* fn, size_t lds, long long rows, const char* name) {
-    int dev = 0, perCU = 0, cus = 0;
-    SBMP_HIP(hipGetDevice(&dev));
-    SBMP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, fn, kRecheckBlock, lds));
-    SBMP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (perCU < 1 || cus < 1)
-        throw Error(SBMP_ERR_HIP, std::string(name) + ": the occupancy query gave no resident workgroup");
-    const long long need = (rows + kRecheckBlock - 1) / kRecheckBlock;
-    return (int)std::min<long long>((long long)std::min(perCU, kRecheckGroupsPerCU) * cus, std::max(need, 1ll));
+// Workgroups of kRecheckBlock lanes for `rows` rows (resident_grid, tree_pass.h).
+template <class Kernel>
+int recheck_grid(Kernel* fn, size_t lds, long long rows, const char* name) {
+    return resident_grid(fn, kRecheckBlock, lds, kRecheckGroupsPerCU, rows, name);
 }
 
 using RecheckFn = decltype(&k_tree_recheck<0, kObsGlobal>);
 
-// The new list's own device copy, NaN scan and grid index, and the copy of the plan's KgmtDev
-// that carries them; freed with the call.
-struct RecheckList {
-    float4* obs = nullptr;
-    int* gridStart = nullptr;
-    float4* gridBoxes = nullptr;
-    ~RecheckList() {
-        if (obs) (void)hipFree(obs);
-        if (gridStart) (void)hipFree(gridStart);
-        if (gridBoxes) (void)hipFree(gridBoxes);
-    }
-    // d: a copy of the plan's parameters and tree pointers; its obstacle fields are replaced.
-    // The form follows begin()'s rule: the grid above kMaxLdsObs boxes (or variant 4), the
-    // global loop only for variant 5.
-    void attach(KgmtDev& d, const float* d_obstacles, int nObs, int variant, hipStream_t s) {
-        d.obstacles = nullptr;
-        d.nObs = nObs;
-        d.obsNaN = 0;
-        d.gridG = 0;
-        d.gridInvW = d.gridInvH = 0.0f;
-        d.gridStart = nullptr;
-        d.gridBoxes = nullptr;
-        if (nObs == 0) return;
-        SBMP_HIP(hipMalloc(reinterpret_cast<void**>(&obs), sizeof(float4) * (size_t)nObs));
-        SBMP_HIP(hipMemcpyAsync(obs, d_obstacles, sizeof(float4) * (size_t)nObs, hipMemcpyDeviceToDevice, s));
-        std::vector<float> h((size_t)4 * nObs);
-        SBMP_HIP(hipMemcpyAsync(h.data(), d_obstacles, sizeof(float) * h.size(), hipMemcpyDeviceToHost, s));
-        SBMP_HIP(hipStreamSynchronize(s));
-        d.obstacles = obs;
-        for (float v : h)   // wave_cull's and grid_free_fast's separation metric need boxes without NaN
-            if (std::isnan(v)) d.obsNaN = 1;
-        if (!((nObs > kMaxLdsObs && variant != 5) || variant == 4)) return;
-        const HostObstacleGrid g =
-            build_obstacle_grid(h.data(), nObs, d.width, d.height, std::min(grid_resolution(nObs), kMaxLdsGridG));
-        // kGridBatch never-met rows past the end: grid_free_fast loads and tests whole batches
-        const size_t nStart = g.start.size(), nBoxes = g.boxes.size() + kGridBatch;
-        std::vector<float4> boxes(nBoxes, make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY));
-        if (!g.boxes.empty()) std::memcpy(boxes.data(), g.boxes.data(), sizeof(float4) * g.boxes.size());
-        SBMP_HIP(hipMalloc(reinterpret_cast<void**>(&gridStart), sizeof(int) * nStart));
-        SBMP_HIP(hipMalloc(reinterpret_cast<void**>(&gridBoxes), sizeof(float4) * nBoxes));
-        SBMP_HIP(hipMemcpy(gridStart, g.start.data(), sizeof(int) * nStart, hipMemcpyHostToDevice));
-        SBMP_HIP(hipMemcpy(gridBoxes, boxes.data(), sizeof(float4) * nBoxes, hipMemcpyHostToDevice));
-        d.gridG = g.g;
-        d.gridInvW = g.invW;
-        d.gridInvH = g.invH;
-        d.gridStart = gridStart;
-        d.gridBoxes = gridBoxes;
-    }
-};
+// The new list's own device copy (in w: freed with the call), NaN scan and grid index, into d:
+// a copy of the plan's parameters and tree pointers whose obstacle fields are replaced.
+// The form follows begin()'s rule: the grid above kMaxLdsObs boxes (or variant 4), the
+// global loop only for variant 5.
+void attach_list(DevBufs& w, KgmtDev& d, const float* d_obstacles, int nObs, int variant, hipStream_t s) {
+    d.obstacles = nullptr;
+    d.nObs = nObs;
+    d.obsNaN = 0;
+    d.gridG = 0;
+    d.gridInvW = d.gridInvH = 0.0f;
+    d.gridStart = nullptr;
+    d.gridBoxes = nullptr;
+    if (nObs == 0) return;
+    float4* obs = w.alloc<float4>((size_t)nObs);
+    SBMP_HIP(hipMemcpyAsync(obs, d_obstacles, sizeof(float4) * (size_t)nObs, hipMemcpyDeviceToDevice, s));
+    std::vector<float> h((size_t)4 * nObs);
+    SBMP_HIP(hipMemcpyAsync(h.data(), d_obstacles, sizeof(float) * h.size(), hipMemcpyDeviceToHost, s));
+    SBMP_HIP(hipStreamSynchronize(s));
+    d.obstacles = obs;
+    for (float v : h)   // wave_cull's and grid_free_fast's separation metric need boxes without NaN
+        if (std::isnan(v)) d.obsNaN = 1;
+    if (!((nObs > kMaxLdsObs && variant != 5) || variant == 4)) return;
+    const HostObstacleGrid g =
+        build_obstacle_grid(h.data(), nObs, d.width, d.height, std::min(grid_resolution(nObs), kMaxLdsGridG));
+    // kGridBatch never-met rows past the end: grid_free_fast loads and tests whole batches
+    const size_t nStart = g.start.size(), nBoxes = g.boxes.size() + kGridBatch;
+    std::vector<float4> boxes(nBoxes, make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY));
+    if (!g.boxes.empty()) std::memcpy(boxes.data(), g.boxes.data(), sizeof(float4) * g.boxes.size());
+    int* gridStart = w.alloc<int>(nStart);
+    float4* gridBoxes = w.alloc<float4>(nBoxes);
+    SBMP_HIP(hipMemcpy(gridStart, g.start.data(), sizeof(int) * nStart, hipMemcpyHostToDevice));
+    SBMP_HIP(hipMemcpy(gridBoxes, boxes.data(), sizeof(float4) * nBoxes, hipMemcpyHostToDevice));
+    d.gridG = g.g;
+    d.gridInvW = g.invW;
+    d.gridInvH = g.invH;
+    d.gridStart = gridStart;
+    d.gridBoxes = gridBoxes;
+}
 
-// Per-call scratch: the status bytes, two anc and two dead arrays and the accumulators.
+// Per-call scratch (in w): the status bytes, two anc and two dead arrays (twoPairs; else only
+// anc[0] and dead[1] are used) and the accumulators.
 struct RecheckScratch {
-    uint8_t* status = nullptr;
+    uint8_t* status;
     int* anc[2] = {nullptr, nullptr};
     uint8_t* dead[2] = {nullptr, nullptr};
-    RecheckAcc* acc = nullptr;
-    ~RecheckScratch() {
-        (void)hipFree(status);
-        (void)hipFree(anc[0]);
-        (void)hipFree(anc[1]);
-        (void)hipFree(dead[0]);
-        (void)hipFree(dead[1]);
-        (void)hipFree(acc);
-    }
-    void alloc(size_t rows, bool twoPairs) {
-        SBMP_HIP(hipMalloc(reinterpret_cast<void**>(&status), rows));
+    RecheckAcc* acc;
+    RecheckScratch(DevBufs& w, size_t rows, bool twoPairs) {
+        status = w.alloc<uint8_t>(rows);
         for (int i = 0; i < 2; ++i) {
-            if (i == 0 || twoPairs) SBMP_HIP(hipMalloc(reinterpret_cast<void**>(&anc[i]), sizeof(int) * rows));
-            if (i == 1 || twoPairs) SBMP_HIP(hipMalloc(reinterpret_cast<void**>(&dead[i]), rows));
+            if (i == 0 || twoPairs) anc[i] = w.alloc<int>(rows);
+            if (i == 1 || twoPairs) dead[i] = w.alloc<uint8_t>(rows);
         }
-        SBMP_HIP(hipMalloc(reinterpret_cast<void**>(&acc), sizeof(RecheckAcc)));
+        acc = w.alloc<RecheckAcc>(1);
     }
 };
 
@@ -337,20 +228,6 @@ int jump_passes(long long bound) {
     return p;
 }
 
-template <int NG>
-void launch_alive_tile(const float4* state, const float4* ctrl, const uint8_t* alive, long long rows, const float* xyt,
-                       int first, int n, QueryAcc* acc, hipStream_t s) {
-    AliveTile<NG> q;
-    for (int g = 0; g < NG; ++g) {
-        const bool real = g < n;
-        q.gx[g] = real ? xyt[3 * (size_t)(first + g)] : 0.0f;
-        q.gy[g] = real ? xyt[3 * (size_t)(first + g) + 1] : 0.0f;
-        q.t[g] = real ? xyt[3 * (size_t)(first + g) + 2] : -1.0f;
-    }
-    const int grid = recheck_grid(reinterpret_cast<const void*>(k_tree_query_alive<NG>), 0, rows, "k_tree_query_alive");
-    hipLaunchKernelGGL(k_tree_query_alive<NG>, dim3(grid), dim3(kRecheckBlock), 0, s, state, ctrl, alive, rows, q, n,
-                       acc + first);
-}
 }  // namespace
 
 void tree_recheck_device(const KgmtDev& base, int agent, int variant, int rows, int depthBound,
@@ -360,26 +237,24 @@ void tree_recheck_device(const KgmtDev& base, int agent, int variant, int rows, 
     if (nObs < 0 || (nObs > 0 && !d_obstacles)) throw Error(SBMP_ERR_INVALID_ARGUMENT, "bad obstacle list");
     if (!out) throw Error(SBMP_ERR_INVALID_ARGUMENT, "out must be non-NULL");
     KgmtDev d = base;   // the plan's own struct, list and grid stay untouched
-    RecheckList list;
-    RecheckScratch w;
-    hipError_t e = hipSuccess;
+    DevBufs listBufs, scratchBufs;   // freed with the call: the scratch first, then the list
     RecheckAcc acc;
-    try {
-        list.attach(d, d_obstacles, nObs, variant, stream);
+    drained_on_throw(stream, [&] {
+        attach_list(listBufs, d, d_obstacles, nObs, variant, stream);
         const int passes = std::max(1, jump_passes(depthBound > 0 ? std::min(depthBound, rows) : rows));
-        w.alloc((size_t)rows, passes > 1);
+        const RecheckScratch w(scratchBufs, (size_t)rows, passes > 1);
         SBMP_HIP(hipMemsetAsync(w.acc, 0, sizeof(RecheckAcc), stream));
         SBMP_HIP(hipMemsetAsync(&w.acc->firstDead, 0xff, sizeof(unsigned), stream));
         with_obs_form(d, variant, [&](auto obs) {
             const RecheckFn fn = (agent == SBMP_AGENT_POINT) ? k_tree_recheck<1, obs.value> : k_tree_recheck<0, obs.value>;
             const size_t lds = (obs.value == kObsLds || obs.value == kObsLds4) ? sizeof(float4) * (size_t)d.nObs : 0;
-            const int grid = recheck_grid(reinterpret_cast<const void*>(fn), lds, rows, "k_tree_recheck");
+            const int grid = recheck_grid(fn, lds, rows, "k_tree_recheck");
             hipLaunchKernelGGL(fn, dim3(grid), dim3(kRecheckBlock), lds, stream, d, (unsigned)rows, w.status, w.anc[0]);
         });
         // pass p reads (anc[p & 1], dead of p) and writes (anc[(p + 1) & 1], dead[(p + 1) & 1]);
         // the dead array of pass 0 is the status bytes themselves
         auto deadIn = [&](int p) { return p == 0 ? w.status : w.dead[p & 1]; };
-        const int gridA = recheck_grid(reinterpret_cast<const void*>(k_tree_alive<false>), 0, rows, "k_tree_alive");
+        const int gridA = recheck_grid(k_tree_alive<false>, 0, rows, "k_tree_alive");
         for (int p = 0; p + 1 < passes; ++p)
             hipLaunchKernelGGL(k_tree_alive<false>, dim3(gridA), dim3(kRecheckBlock), 0, stream, w.anc[p & 1],
                                (const uint8_t*)deadIn(p), w.anc[(p + 1) & 1], w.dead[(p + 1) & 1], rows,
@@ -390,15 +265,8 @@ void tree_recheck_device(const KgmtDev& base, int agent, int variant, int rows, 
                            (const uint8_t*)deadIn(last), (int*)nullptr, exported, rows, (const uint8_t*)w.status, d_alive,
                            w.acc);
         SBMP_HIP(hipGetLastError());
-        e = hipMemcpyAsync(&acc, w.acc, sizeof(acc), hipMemcpyDeviceToHost, stream);
-        if (status && e == hipSuccess) e = hipMemcpyAsync(status, exported, (size_t)rows, hipMemcpyDeviceToHost, stream);
-        const hipError_t e2 = hipStreamSynchronize(stream);
-        if (e == hipSuccess) e = e2;
-    } catch (...) {
-        (void)hipStreamSynchronize(stream);   // nothing in flight when the scratch is freed
-        throw;
-    }
-    SBMP_HIP(e);
+        read_back(stream, {{&acc, w.acc, sizeof(acc)}, {status, exported, (size_t)rows}});
+    });
     out->rows = rows;
     out->alive = (int)acc.alive;
     out->blocked = (int)acc.blocked;
@@ -422,21 +290,14 @@ void check_recheck_args(const sbmp_tree_recheck_args* a, const sbmp_tree_recheck
 
 void tree_recheck_batch(const sbmp_tree_recheck_args* a, uint8_t* status, sbmp_tree_recheck* out, hipStream_t stream) {
     check_recheck_args(a, out);
-    // what the Euler loops read of a plan (KgmtPlanner's constructor sets the same fields)
     KgmtDev d{};
-    d.numDisc = a->numDisc;
+    set_euler_params(d, a->numDisc, a->agentLength);
     d.width = a->width;
     d.height = a->height;
-    d.agentLength = a->agentLength;
-    int ex = 0;
-    d.invAgentLength = (std::frexp(a->agentLength, &ex) == 0.5f) ? 1.0f / a->agentLength : 0.0f;
-    d.rcpNumDisc = markstein_rcp((float)a->numDisc);
-    d.rcpAgentLength = markstein_rcp(a->agentLength);
     d.treeState = reinterpret_cast<float4*>(const_cast<float*>(a->state));
     d.treeCtrl = reinterpret_cast<float4*>(const_cast<float*>(a->ctrl));
     d.treeParent = const_cast<int*>(a->parent);
-    int variant = 0;   // SBMP_EXPAND_VARIANT, as the planner reads it
-    if (const char* v = getenv("SBMP_EXPAND_VARIANT")) variant = std::min(5, std::max(0, atoi(v)));
+    const int variant = expand_variant_from_env();
     tree_recheck_device(d, a->agent, variant, a->rows, a->depthBound, a->obstacles, a->obstaclesCount, nullptr, status,
                         out, stream);
 }
@@ -446,48 +307,6 @@ void tree_recheck_batch_host(const sbmp_tree_recheck_args* a, uint8_t* status, s
     std::vector<uint8_t> alive((size_t)a->rows);
     recheck_rows_host(a->state, a->ctrl, a->parent, a->rows, a->agent, a->numDisc, a->agentLength, a->width, a->height,
                       a->obstacles, a->obstaclesCount, alive.data(), status, out);
-}
-
-void tree_query_alive_device(const float* d_state, const float* d_ctrl, const uint8_t* d_alive, long long rows,
-                             const sbmp_goal_query* goals, int count, sbmp_goal_answer* out, hipStream_t stream) {
-    tree_query_check_goals(goals, count, out);
-    if (!d_state || !d_ctrl || !d_alive) throw Error(SBMP_ERR_INVALID_ARGUMENT, "state, ctrl and alive must be non-NULL");
-    if (rows < 1 || rows > 0x7fffffffll) throw Error(SBMP_ERR_INVALID_ARGUMENT, "rows must be in [1, 2^31)");
-    if (count == 0) return;
-    std::vector<float> xyt(3 * (size_t)count);
-    for (int i = 0; i < count; ++i) {
-        xyt[3 * (size_t)i] = goals[i].x;
-        xyt[3 * (size_t)i + 1] = goals[i].y;
-        xyt[3 * (size_t)i + 2] = goal_radius_threshold(goals[i].radius);
-    }
-    const float4* state = reinterpret_cast<const float4*>(d_state);
-    const float4* ctrl = reinterpret_cast<const float4*>(d_ctrl);
-    std::vector<QueryAcc> host(count);
-    QueryAcc* acc = nullptr;
-    SBMP_HIP(hipMalloc(reinterpret_cast<void**>(&acc), sizeof(QueryAcc) * (size_t)count));
-    hipError_t e = hipSuccess;
-    try {
-        hipLaunchKernelGGL(k_tree_query_alive_init, dim3((count + 255) / 256), dim3(256), 0, stream, acc, count);
-        for (int first = 0; first < count;) {   // tiles of 8 (its centres and thresholds still fit the SGPRs), 4, 1
-            const int left = count - first;
-            const int n = left >= 8 ? 8 : left >= 4 ? 4 : 1;
-            if (n == 8) launch_alive_tile<8>(state, ctrl, d_alive, rows, xyt.data(), first, n, acc, stream);
-            else if (n == 4) launch_alive_tile<4>(state, ctrl, d_alive, rows, xyt.data(), first, n, acc, stream);
-            else launch_alive_tile<1>(state, ctrl, d_alive, rows, xyt.data(), first, n, acc, stream);
-            first += n;
-        }
-        SBMP_HIP(hipGetLastError());
-        e = hipMemcpyAsync(host.data(), acc, sizeof(QueryAcc) * (size_t)count, hipMemcpyDeviceToHost, stream);
-        const hipError_t e2 = hipStreamSynchronize(stream);
-        if (e == hipSuccess) e = e2;
-    } catch (...) {
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(acc);
-        throw;
-    }
-    (void)hipFree(acc);
-    SBMP_HIP(e);
-    for (int i = 0; i < count; ++i) out[i] = goal_answer_of(host[i].count, host[i].first, host[i].best, host[i].nearest);
 }
 
 }  // namespace sbmp

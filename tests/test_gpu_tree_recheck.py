@@ -153,6 +153,46 @@ def test_recheck_of_the_demo_plan(seed, obstacles):
     assert_same_answers(g.query_goals(goals), model_of_rows(state, ctrl, goals), label="the unmasked query is unchanged")
 
 
+ALIVE_GOAL_COUNTS = (1, 3, 4, 7, 8, 9, 13, 17)
+
+
+def _lattice_goals(count):
+    """The first `count` points of a 5 x 5 lattice of pitch 4 over the 20 x 20 workspace, the
+    root's own point (5, 5) first.  Radii alternate: 1.5 (the root, always alive, lies inside
+    goal 0) and 0.001 (no row comes that close to a lattice point)."""
+    pts = [((5 + 4 * i) % 20, (5 + 4 * j) % 20) for j in range(5) for i in range(5)][:count]
+    return np.array([[x, y, 1.5 if k % 2 == 0 else 0.001] for k, (x, y) in enumerate(pts)], np.float32)
+
+
+@pytest.fixture(scope="module")
+def rechecked_plan(obstacles):
+    """One grown plan, re-checked against the other box list, and the model of that re-check."""
+    g = _mk(**BASE)
+    g.plan(DEMO_INITIAL, DEMO_GOAL, _dev(obstacles), len(obstacles), seed=BASE_SEED)
+    other = random_boxes(600, 20.0, 20.0, 7, 0.3, 0.8)
+    got = g.recheck(other)
+    (want, wsum, alive), (state, ctrl, _) = _model_of_tree(g, other)
+    assert_same_recheck(got, (want, wsum), label="the re-check under the masked queries")
+    return g, state, ctrl, alive
+
+
+@pytest.mark.parametrize("count", ALIVE_GOAL_COUNTS)
+def test_masked_query_over_every_tile_of_the_ladder(count, rechecked_plan):
+    """query_goals(alive=True) for goal counts that launch every tile of the masked query's
+    ladder (8, 4, 1) alone, repeated and behind one another: 17 = 8 + 8 + 1, 13 = 8 + 4 + 1,
+    7 = 4 + 1 + 1 + 1.  Field for field against the model over the alive rows.  Some goal has
+    rows inside and, from two goals on (one goal cannot be both), some goal has none."""
+    g, state, ctrl, alive = rechecked_plan
+    assert alive.any() and not alive.all()                        # the mask is mixed
+    goals = _lattice_goals(count)
+    a = g.query_goals(goals, alive=True)
+    print(f"{count} goals: count {a['count'].tolist()}")
+    assert_same_answers(a, _alive_answers(state, ctrl, alive, goals), label=f"{count} goals alive")
+    assert (a["count"] > 0).any()
+    if count >= 2:
+        assert (a["count"] == 0).any()
+
+
 def test_recheck_between_steps_changes_nothing(obstacles):
     kw = dict(BASE)
     other = random_boxes(600, 20.0, 20.0, 7, 0.3, 0.8)
