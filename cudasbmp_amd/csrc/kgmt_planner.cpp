@@ -671,8 +671,8 @@ void KgmtPlanner::begin(const float* initial, const float* goal, const float* d_
     poll_->word = 0;   // no k_step of this plan has run (the stream is idle)
     if (ex_) ex_->barrier(s);   // every rank set up before the first (time-bounded) exchange
     t0_ = now_ms();
-    if (d.stepMode) flushed_ = false;   // k_step(1) plans iteration 1 itself
-    else launch_finish(d, 0, 0, s, timing(K_FINISH));   // prepares iteration 1
+    flushed_ = !d.stepMode;   // k_step(1) plans iteration 1 itself; two launches: nothing is ever pending
+    if (!d.stepMode) launch_finish(d, 0, 0, s, timing(K_FINISH));   // prepares iteration 1
     SBMP_HIP(hipGetLastError());
 }
 
@@ -761,6 +761,9 @@ void KgmtPlanner::path_info(sbmp_path_info* out) {
 
 void KgmtPlanner::build_grid(const float* d_obstacles, int nObs) {
     KgmtDev& d = d_;
+    // The copies below run outside the planner's (non-blocking) stream: iterations of the last
+    // plan that were enqueued and never waited for may still read the tables they overwrite.
+    SBMP_HIP(hipStreamSynchronize(stream_));
     {
         std::vector<float> h((size_t)4 * nObs);
         SBMP_HIP(hipMemcpy(h.data(), d_obstacles, sizeof(float) * h.size(), hipMemcpyDeviceToHost));

@@ -170,13 +170,24 @@ sbmp_status sbmp_kgmt_destroy(sbmp_kgmt* h);
  * KGMT.cu:111 — the reference seeds with time(NULL); here the seed is explicit),
  * iterate until goal / full tree / numIterations.  initial and goal are host
  * arrays of 7 floats; d_obstacles is a device array of obstaclesCount boxes
- * [xmin, ymin, xmax, ymax] (reference collisionCheck.cu:7-14).  Blocking. */
+ * [xmin, ymin, xmax, ymax] (reference collisionCheck.cu:7-14).  Blocking.
+ * plan is begin + the loop, so begin's reuse contract (below) holds: any number of plans
+ * on one handle, each with its own start, goal, seed and obstacle list. */
 sbmp_status sbmp_kgmt_plan(sbmp_kgmt* h, const float initial[7], const float goal[7], const float* d_obstacles,
                            int obstaclesCount, uint64_t seed, sbmp_plan_result* result);
 
 /* Stepwise form of plan: begin = prologue (KGMT.cu:84-116); step enqueues up to
  * `iterations` more loop iterations and waits for them (*active = 0 once the
- * loop has ended); result reads the outcome. */
+ * loop has ended); result reads the outcome.
+ * Reuse: begin may be called on a handle in any state -- never begun, finished,
+ * mid-plan, or with iterations enqueued and not waited for (they are ordered before
+ * begin's own work on the handle's stream and their results are dropped).  The plan that
+ * follows is the one a fresh handle of the same parameters would compute, bit for bit.
+ * The obstacle list may change in length and in form (registers, LDS, grid, none) from
+ * call to call.  The caller's array is copied during the call: on return it may be
+ * overwritten or freed.  The alive mask of a re-check (sbmp_kgmt_recheck_tree) does not
+ * survive begin: sbmp_kgmt_query_goals_alive fails with SBMP_ERR_STATE until the next
+ * re-check.  tests/test_gpu_reuse_scenarios.py holds the contract. */
 sbmp_status sbmp_kgmt_begin(sbmp_kgmt* h, const float initial[7], const float goal[7], const float* d_obstacles,
                             int obstaclesCount, uint64_t seed);
 sbmp_status sbmp_kgmt_step(sbmp_kgmt* h, int iterations, int* active);
@@ -562,7 +573,13 @@ sbmp_status sbmp_kgmt_batch_destroy(sbmp_kgmt_batch* h);
 /* initials, goals: host arrays of count x 7 floats; seeds: count; results: count, or NULL.
  * A NULL array or a non-finite root (x, y, theta, v) of any member fails with
  * SBMP_ERR_INVALID_ARGUMENT before anything is launched.  plan blocks until every member has
- * ended (goal, full tree or numIterations); a member's wallMs is taken at its own end. */
+ * ended (goal, full tree or numIterations); a member's wallMs is taken at its own end.
+ * Reuse: as sbmp_kgmt_begin states it, for every member.  batch_begin / batch_plan may be
+ * called on a batch in any state (never begun, finished, mid-plan, iterations enqueued and
+ * not waited for); every member then computes what a fresh planner would, bit for bit; the
+ * obstacle list may change in length and form from call to call (the packing into launches
+ * is chosen again at every begin, sbmp_batch_info) and is copied during the call; a
+ * member's alive mask does not survive it. */
 sbmp_status sbmp_kgmt_batch_plan(sbmp_kgmt_batch* h, const float* initials, const float* goals,
                                  const float* d_obstacles, int obstaclesCount, const uint64_t* seeds,
                                  sbmp_plan_result* results);

@@ -37,7 +37,7 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _rank_main(rank, port, kw, seed, out_dir, exchange, delay=0.0):
+def _rank_main(rank, port, kw, seed, out_dir, exchange, delay=0.0, before=()):
     import sys
     import time
     sys.path.insert(0, ROOT)
@@ -80,6 +80,9 @@ def _rank_main(rank, port, kw, seed, out_dir, exchange, delay=0.0):
     if rank == 1 and delay:
         time.sleep(delay)   # process skew before the first exchange (begin() holds a host barrier)
     g.set_profiling(True)   # counts the launches: which exchange ran
+    for other_seed, unwaited in before:   # predecessors on the same handle: begun, enqueued, never waited for
+        g.begin(DEMO_INITIAL, DEMO_GOAL, DeviceBuffer(obs), len(obs), other_seed)
+        g.enqueue(unwaited)
     r = g.plan(DEMO_INITIAL, DEMO_GOAL, DeviceBuffer(obs), len(obs), seed=seed)
     oneshots = g.kernel_stats().get("k_oneshot", (0, 0.0))[0]
     pinfo = g.path_info()
@@ -99,39 +102,49 @@ def _rank_main(rank, port, kw, seed, out_dir, exchange, delay=0.0):
     dist.destroy_process_group()
 
 
+# the 4,096-slot fill configuration most cases run
+FILL_4096 = dict(samplesPerIteration=4096, batchRule="fill", maxTreeSize=200000, numIterations=15, goalThreshold=0.0)
+
+
 @pytest.mark.parametrize("kw,seed,exchange,delay", [
     (dict(), 3, "oneshot", 0.0),
-    (dict(samplesPerIteration=4096, batchRule="fill", maxTreeSize=200000, numIterations=15, goalThreshold=0.0), 21,
-     "oneshot", 0.0),
+    (FILL_4096, 21, "oneshot", 0.0),
     (dict(fixGNewClear=True, numIterations=40), 8, "oneshot", 0.0),
     (dict(), 3, "collective", 0.0),
-    (dict(samplesPerIteration=4096, batchRule="fill", maxTreeSize=200000, numIterations=15, goalThreshold=0.0), 21,
-     "collective", 0.0),
-    (dict(samplesPerIteration=4096, batchRule="fill", maxTreeSize=200000, numIterations=15, goalThreshold=0.0), 21,
-     "oneshot-remote", 0.0),
-    (dict(samplesPerIteration=4096, batchRule="fill", maxTreeSize=200000, numIterations=15, goalThreshold=0.0), 21,
-     "oneshot-kernel", 0.0),
+    (FILL_4096, 21, "collective", 0.0),
+    (FILL_4096, 21, "oneshot-remote", 0.0),
+    (FILL_4096, 21, "oneshot-kernel", 0.0),
     (dict(fixGNewClear=True, numIterations=40), 8, "oneshot-kernel", 0.0),
     # rank 1 starts 3 s late (round 2's exchange gave up after 1 s)
-    (dict(samplesPerIteration=4096, batchRule="fill", maxTreeSize=200000, numIterations=15, goalThreshold=0.0), 21,
-     "oneshot", 3.0),
+    (FILL_4096, 21, "oneshot", 3.0),
     # rank 1's start-up check of the one-shot exchange fails: both ranks must switch to the
     # all-reduce together (one rank alone would leave the other waiting for its flags)
-    (dict(samplesPerIteration=4096, batchRule="fill", maxTreeSize=200000, numIterations=15, goalThreshold=0.0), 21,
-     "oneshot-check-fails", 0.0),
+    (FILL_4096, 21, "oneshot-check-fails", 0.0),
     # rank 1's start-up check of the list mirror fails: both ranks must drop the mirror (and with
     # it the fused exchange) together and read the lists over the mapping with k_oneshot
-    (dict(samplesPerIteration=4096, batchRule="fill", maxTreeSize=200000, numIterations=15, goalThreshold=0.0), 21,
-     "mirror-check-fails", 0.0),
+    (FILL_4096, 21, "mirror-check-fails", 0.0),
     # rank 1's start-up check of the fused exchange's in-kernel order fails: both ranks keep
     # the mirror and run the exchange as its own k_oneshot launch, together
-    (dict(samplesPerIteration=4096, batchRule="fill", maxTreeSize=200000, numIterations=15, goalThreshold=0.0), 21,
-     "fused-check-fails", 0.0),
+    (FILL_4096, 21, "fused-check-fails", 0.0),
 ])
 def test_two_processes_one_gpu_bit_exact(kw, seed, exchange, delay, tmp_path, obstacles, oracle_lib):
+    _run_ranks_and_compare(kw, seed, exchange, delay, tmp_path, obstacles)
+
+
+@pytest.mark.parametrize("exchange", ["oneshot", "collective"])
+def test_two_processes_used_handle_bit_exact(exchange, tmp_path, obstacles, oracle_lib):
+    """The plan whose state is compared runs on a used handle: its predecessor (the same
+    obstacles, another seed) was begun, three iterations were enqueued and never waited for,
+    so the exchange sequence numbers carry on across begin() and both inbox parities, the list
+    mirrors and the record buffers hold another plan's words.  The comparison with the oracle's
+    fresh run is the one above."""
+    _run_ranks_and_compare(FILL_4096, 21, exchange, 0.0, tmp_path, obstacles, before=((22, 3),))
+
+
+def _run_ranks_and_compare(kw, seed, exchange, delay, tmp_path, obstacles, before=()):
     ctx = mp.get_context("spawn")
     port = _free_port()
-    procs = [ctx.Process(target=_rank_main, args=(r, port, kw, seed, str(tmp_path), exchange, delay))
+    procs = [ctx.Process(target=_rank_main, args=(r, port, kw, seed, str(tmp_path), exchange, delay, before))
              for r in range(WORLD)]
     for pr in procs:
         pr.start()
