@@ -4,6 +4,10 @@ Mirrors the reference's KGMT interface (reference include/planners/KGMT.cuh:28-3
 ctor(width, height, N, n, numIterations, maxTreeSize, numDisc, agentLength,
 goalThreshold), plan(initial, goal, obstacles, obstaclesCount)) with an explicit
 curand seed, plus state accessors in the reference's array layouts.
+
+ref_lib() and the ref_* / header_* functions at the end bind oracle/_ref/libkgmt_ref.so: the
+reference's own per-child functions, compiled unmodified for the host by `make -C oracle ref`
+(oracle/ref_shim), which the restatement above is held to.
 """
 from __future__ import annotations
 
@@ -16,7 +20,9 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "_build", "libkgmt_oracle.so")
+_REF_LIB_PATH = os.path.join(_HERE, "_ref", "libkgmt_ref.so")
 _lib = None
+_ref_lib = None
 
 
 class OracleParams(ctypes.Structure):
@@ -43,14 +49,67 @@ class OracleIterLog(ctypes.Structure):
                 ("itr", "treeSizeBefore", "nG", "k", "nExp", "S", "A", "treeSizeAfter", "goalIdx")]
 
 
+def reference_dir() -> str:
+    """Where the reference tree is looked for (the Makefile's SBMP_REFERENCE_DIR)."""
+    return os.environ.get("SBMP_REFERENCE_DIR", "/root/reference")
+
+
+_REF_SOURCES = ("src/statePropagator/statePropagator.cu", "src/collisionCheck/collisionCheck.cu",
+                "src/planners/KGMT.cu")
+
+
+def reference_tree_present() -> bool:
+    """The three reference files the `ref` target compiles are there and readable."""
+    return all(os.access(os.path.join(reference_dir(), f), os.R_OK) for f in _REF_SOURCES)
+
+
 def build(quiet: bool = True) -> str:
-    """Compile the oracle with its Makefile (g++, no GPU needed)."""
+    """Compile the oracle with its Makefile (g++, no GPU needed), and, where the reference tree
+    exists, the reference's own per-child functions as well (build_ref)."""
     out = subprocess.run(["make", "-C", _HERE], capture_output=True, text=True)
     if out.returncode != 0:
         raise RuntimeError("oracle build failed:\n" + out.stdout + out.stderr)
     if not quiet:
         print(out.stdout)
+    if reference_tree_present():
+        build_ref(quiet)
     return _LIB_PATH
+
+
+def build_ref(quiet: bool = True) -> str:
+    """Compile oracle/_ref/libkgmt_ref.so from the reference tree (the Makefile's `ref` target)."""
+    out = subprocess.run(["make", "-C", _HERE, "ref", "SBMP_REFERENCE_DIR=" + reference_dir()],
+                         capture_output=True, text=True)
+    if out.returncode != 0:
+        raise RuntimeError("reference build failed:\n" + out.stdout + out.stderr)
+    if not quiet:
+        print(out.stdout)
+    return _REF_LIB_PATH
+
+
+def ref_lib():
+    """The reference's per-child functions, host-compiled.  Built when the reference tree is there;
+    without the tree an already built library is used as it is, and a missing one is an error."""
+    global _ref_lib
+    if _ref_lib is None:
+        if reference_tree_present():
+            build_ref()
+        elif not os.path.exists(_REF_LIB_PATH):
+            raise FileNotFoundError(f"{_REF_LIB_PATH} is not built and there is no reference tree at "
+                                    f"{reference_dir()} to build it from")
+        L = ctypes.CDLL(_REF_LIB_PATH)
+        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+        L.ref_expand.argtypes = [vp, vp, i, i, f, vp, i, f, f, vp, vp]
+        L.ref_cells.argtypes = [vp, i, f, i, f, i, vp, vp]
+        L.hdr_cells.argtypes = L.ref_cells.argtypes
+        L.ref_goal.argtypes = [vp, i, vp, f, vp]
+        L.hdr_goal.argtypes = [vp, i, vp, f, vp, vp]
+        L.ref_cost.argtypes = [vp, vp, i, vp]
+        L.ref_motion_valid.argtypes = [vp, vp, i, vp, i, vp]
+        for name in ("ref_expand", "ref_cells", "hdr_cells", "ref_goal", "hdr_goal", "ref_cost", "ref_motion_valid"):
+            getattr(L, name).restype = None
+        _ref_lib = L
+    return _ref_lib
 
 
 def lib():
@@ -343,3 +402,84 @@ def tanf(x: np.ndarray):
     t = np.zeros_like(x)
     lib().oracle_tanf(_fp(x), len(x), _fp(t))
     return t
+
+
+# ---------------------------------------------------------------- the reference's own text (ref_lib)
+def _obs4(obstacles) -> np.ndarray:
+    # one spare row, so that an empty list still has an address
+    obs = np.ascontiguousarray(obstacles, dtype=np.float32).reshape(-1, 4)
+    return obs if len(obs) else np.zeros((1, 4), dtype=np.float32)
+
+
+def ref_expand(parents, rng, obstacles, numDisc=10, agentLength=1.0, width=20.0, height=20.0) -> dict:
+    """The reference's propagateAndCheck over a batch: parents (n, 7), rng (n, 6) uint32 XORWOW
+    states -> children (n, 7), valid and the advanced RNG states (three draws each)."""
+    par = np.ascontiguousarray(parents, dtype=np.float32).reshape(-1, 7)
+    st = np.ascontiguousarray(rng, dtype=np.uint32).reshape(-1, 6).copy()
+    assert len(par) == len(st)
+    count = len(np.asarray(obstacles).reshape(-1, 4))
+    obs = _obs4(obstacles)
+    n = len(par)
+    children = np.zeros((n, 7), dtype=np.float32)
+    valid = np.zeros(n, dtype=np.uint8)
+    ref_lib().ref_expand(_fp(par), _fp(st), n, int(numDisc), float(agentLength), _fp(obs), count, float(width),
+                         float(height), _fp(children), _fp(valid))
+    return {"children": children, "valid": valid.astype(bool), "rng": st}
+
+
+def _cells(fn, xy, R1Size, N, R2Size, n):
+    xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+    r1 = np.zeros(len(xy), dtype=np.int32)
+    r2 = np.zeros(len(xy), dtype=np.int32)
+    fn(_fp(xy), len(xy), float(R1Size), int(N), float(R2Size), int(n), _fp(r1), _fp(r2))
+    return r1, r2
+
+
+def ref_cells(xy, R1Size, N, R2Size, n):
+    """The reference's getR1 / getR2 over xy (k, 2) -> (r1, r2).  The caller keeps every x / R1Size
+    finite and inside int range: outside it the reference's conversion is undefined."""
+    return _cells(ref_lib().ref_cells, xy, R1Size, N, R2Size, n)
+
+
+def header_cells(xy, R1Size, N, R2Size, n):
+    """sbmp::getR1 / getR2 (include/sbmp/grid.h) on the host over the same arrays."""
+    return _cells(ref_lib().hdr_cells, xy, R1Size, N, R2Size, n)
+
+
+def ref_goal(xy, goal, r) -> np.ndarray:
+    """The reference's inGoalRegion over xy (k, 2)."""
+    xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+    g = np.ascontiguousarray(np.asarray(goal, dtype=np.float32)[:2])
+    out = np.zeros(len(xy), dtype=np.uint8)
+    ref_lib().ref_goal(_fp(xy), len(xy), _fp(g), float(np.float32(r)), _fp(out))
+    return out.astype(bool)
+
+
+def header_goal(xy, goal, r):
+    """(sbmp::inGoalRegion, goal_inside(goal_d2(..))) of the public headers on the host."""
+    xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+    g = np.ascontiguousarray(np.asarray(goal, dtype=np.float32)[:2])
+    a = np.zeros(len(xy), dtype=np.uint8)
+    b = np.zeros(len(xy), dtype=np.uint8)
+    ref_lib().hdr_goal(_fp(xy), len(xy), _fp(g), float(np.float32(r)), _fp(a), _fp(b))
+    return a.astype(bool), b.astype(bool)
+
+
+def ref_cost(x0, x1) -> np.ndarray:
+    """The reference's getCost over rows of 7."""
+    x0 = np.ascontiguousarray(x0, dtype=np.float32).reshape(-1, 7)
+    x1 = np.ascontiguousarray(x1, dtype=np.float32).reshape(-1, 7)
+    out = np.zeros(len(x1), dtype=np.float32)
+    ref_lib().ref_cost(_fp(x0), _fp(x1), len(x1), _fp(out))
+    return out
+
+
+def ref_motion_valid(bbMin, bbMax, obstacles) -> np.ndarray:
+    """The reference's isMotionValid over step boxes bbMin, bbMax (k, 2)."""
+    lo = np.ascontiguousarray(bbMin, dtype=np.float32).reshape(-1, 2)
+    hi = np.ascontiguousarray(bbMax, dtype=np.float32).reshape(-1, 2)
+    count = len(np.asarray(obstacles).reshape(-1, 4))
+    obs = _obs4(obstacles)
+    out = np.zeros(len(lo), dtype=np.uint8)
+    ref_lib().ref_motion_valid(_fp(lo), _fp(hi), len(lo), _fp(obs), count, _fp(out))
+    return out.astype(bool)
