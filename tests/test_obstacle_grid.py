@@ -2,8 +2,17 @@
 the grid answer equals the reference's all-boxes isMotionValid
 (collisionCheck.cu:6-28) for every segment, evaluated on the host through
 sbmp_obstacle_grid_query and compared with a numpy brute force of the same
-predicate (float32 compares, NaN compares false).  The device kernels share the
-query template; tests/test_gpu_parity.py runs the planner on the grid path."""
+predicate (float32 compares, NaN compares false).
+
+That entry runs the host template grid_motion_valid, and only that.  The kernels
+walk the same index with other code (grid_run / grid_run_sep / grid_free_at of
+cudasbmp_amd/csrc/kgmt_device.h, and grid_motion_valid_batched for a list with a
+NaN box): tests/test_gpu_grid_cases.py holds those to the same brute force, in
+test_polyline_bytes_equal_the_model (crafted segments through
+sbmp_tree_recheck_batch, B = 4 and the batched form) and test_scenario_bit_exact
+(planner runs, k_step's B = 8 walk over the LDS table), and
+tests/test_grid_cases_oracle.py proves what those cases cover.
+tests/test_gpu_parity.py runs the planner on the grid path over c5."""
 import ctypes
 import os
 
