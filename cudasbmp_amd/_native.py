@@ -157,6 +157,7 @@ EXPORTED_SYMBOLS = (
     "sbmp_kgmt_recheck_tree", "sbmp_kgmt_query_goals_alive", "sbmp_tree_recheck_batch", "sbmp_tree_recheck_batch_host",
     "sbmp_kgmt_solution_paths", "sbmp_kgmt_trace_rows", "sbmp_tree_paths_batch", "sbmp_tree_paths_batch_host",
     "sbmp_tree_trace_batch", "sbmp_tree_trace_batch_host",
+    "sbmp_tree_query_alive_batch", "sbmp_tree_query_alive_batch_host",
 )
 
 _lib = None
@@ -243,6 +244,8 @@ def lib():
         "sbmp_kgmt_query_goals": [vp, vp, i, vp],
         "sbmp_tree_query_batch": [vp, vp, ctypes.c_longlong, vp, i, vp, vp],
         "sbmp_tree_query_batch_host": [vp, vp, ctypes.c_longlong, vp, i, vp],
+        "sbmp_tree_query_alive_batch": [vp, vp, vp, ctypes.c_longlong, vp, i, vp, vp],
+        "sbmp_tree_query_alive_batch_host": [vp, vp, vp, ctypes.c_longlong, vp, i, vp],
         "sbmp_goal_radius_threshold": [ctypes.c_float, P(ctypes.c_float)],
         "sbmp_kgmt_recheck_tree": [vp, vp, i, vp, i, P(TreeRecheck)],
         "sbmp_kgmt_query_goals_alive": [vp, vp, i, vp],

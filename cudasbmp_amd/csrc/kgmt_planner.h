@@ -129,7 +129,8 @@ void tree_query_alive_device(const float* d_state, const float* d_ctrl, const ui
                              const sbmp_goal_query* goals, int count, sbmp_goal_answer* out, hipStream_t stream);
 void tree_query_host(const float* state, const float* ctrl, long long rows, const sbmp_goal_query* goals, int count,
                      sbmp_goal_answer* out);
-sbmp_goal_answer goal_answer_of(unsigned count, unsigned first, unsigned long long best, unsigned long long nearest);
+void tree_query_alive_host(const float* state, const float* ctrl, const uint8_t* alive, long long rows,
+                           const sbmp_goal_query* goals, int count, sbmp_goal_answer* out);
 
 // The tree re-check (tree_recheck.hip; include/sbmp/tree_recheck.h).  base: the plan's
 // parameters and tree pointers; only a copy with the obstacle fields replaced reaches the

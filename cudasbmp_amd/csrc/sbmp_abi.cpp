@@ -203,6 +203,20 @@ sbmp_status sbmp_tree_query_batch_host(const float* state, const float* ctrl, lo
     return guarded([&] { sbmp::tree_query_host(state, ctrl, rows, goals, count, out); });
 }
 
+sbmp_status sbmp_tree_query_alive_batch(const float* d_state, const float* d_ctrl, const uint8_t* d_alive,
+                                        long long rows, const sbmp_goal_query* goals, int count,
+                                        sbmp_goal_answer* out, void* stream) {
+    return guarded([&] {
+        sbmp::tree_query_alive_device(d_state, d_ctrl, d_alive, rows, goals, count, out, static_cast<hipStream_t>(stream));
+    });
+}
+
+sbmp_status sbmp_tree_query_alive_batch_host(const float* state, const float* ctrl, const uint8_t* alive,
+                                             long long rows, const sbmp_goal_query* goals, int count,
+                                             sbmp_goal_answer* out) {
+    return guarded([&] { sbmp::tree_query_alive_host(state, ctrl, alive, rows, goals, count, out); });
+}
+
 sbmp_status sbmp_tree_recheck_batch(const sbmp_tree_recheck_args* args, uint8_t* status, sbmp_tree_recheck* out,
                                     void* stream) {
     return guarded([&] { sbmp::tree_recheck_batch(args, status, out, static_cast<hipStream_t>(stream)); });

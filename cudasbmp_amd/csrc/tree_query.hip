@@ -6,6 +6,7 @@
 //                            alive: one masked row per lane, tiles of 8, 4 and 1
 //   sbmp_tree_query_batch    the kernel over caller rows (tree_query_device)
 //   sbmp_tree_query_batch_host   a plain host loop with the literal rule (tree_query_host)
+//   sbmp_tree_query_alive_batch / _host   the masked kernel and the masked loop over caller rows
 //   sbmp_kgmt_query_goals    the kernel over a planner's tree (KgmtPlanner::query_goals)
 //   sbmp_kgmt_query_goals_alive  the masked kernel (KgmtPlanner::query_goals_alive)
 // The kernels read treeState once, 16 B per row; a row's cost (treeCtrl.w) is read only by
@@ -340,17 +341,6 @@ void goal_query_device(const sbmp_goal_query* goals, int count, sbmp_goal_answer
 
 }  // namespace
 
-sbmp_goal_answer goal_answer_of(unsigned count, unsigned first, unsigned long long best, unsigned long long nearest) {
-    sbmp_goal_answer a;
-    a.count = (int)count;
-    a.firstRow = count ? (int)first : -1;
-    a.bestRow = count ? (int)(uint32_t)best : -1;
-    a.bestCost = count ? u2f((uint32_t)(best >> 32)) : 0.0f;
-    a.nearestRow = (int)(uint32_t)nearest;
-    a.nearestDistance = __builtin_sqrtf(u2f((uint32_t)(nearest >> 32)));
-    return a;
-}
-
 void launch_tree_query(const float4* state, const float4* ctrl, long long rows, const float* goalsXYT, int count,
                        QueryAcc* acc, hipStream_t s) {
     if (count <= 0) return;
@@ -406,27 +396,21 @@ void tree_query_alive_device(const float* d_state, const float* d_ctrl, const ui
     });
 }
 
-// The literal rule, row by row (no threshold): what the kernel must reproduce.
+// The literal rule, row by row (query_rows_host, include/sbmp/tree_query.h).
 void tree_query_host(const float* state, const float* ctrl, long long rows, const sbmp_goal_query* goals, int count,
                      sbmp_goal_answer* out) {
     tree_query_check_goals(goals, count, out);
     if (!state || !ctrl) throw Error(SBMP_ERR_INVALID_ARGUMENT, "state and ctrl must be non-NULL");
     check_query_rows(rows);
-    for (int i = 0; i < count; ++i) {
-        unsigned n = 0u, first = ~0u;
-        unsigned long long best = kNoGoalKey, nearest = kNoGoalKey;
-        for (long long row = 0; row < rows; ++row) {
-            const float d2 = goal_d2(state[4 * row], state[4 * row + 1], goals[i].x, goals[i].y);
-            const unsigned long long nk = goal_key(d2, (uint32_t)row);
-            if (nk < nearest) nearest = nk;
-            if (!goal_inside(d2, goals[i].radius)) continue;
-            ++n;
-            if ((unsigned)row < first) first = (unsigned)row;
-            const unsigned long long bk = goal_key(ctrl[4 * row + 3], (uint32_t)row);
-            if (bk < best) best = bk;
-        }
-        out[i] = goal_answer_of(n, first, best, nearest);
-    }
+    query_rows_host(state, ctrl, nullptr, rows, goals, count, out);
+}
+
+void tree_query_alive_host(const float* state, const float* ctrl, const uint8_t* alive, long long rows,
+                           const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) {
+    tree_query_check_goals(goals, count, out);
+    if (!state || !ctrl || !alive) throw Error(SBMP_ERR_INVALID_ARGUMENT, "state, ctrl and alive must be non-NULL");
+    check_query_rows(rows);
+    query_rows_host(state, ctrl, alive, rows, goals, count, out);
 }
 
 }  // namespace sbmp

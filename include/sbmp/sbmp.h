@@ -253,6 +253,10 @@ typedef struct sbmp_goal_answer {
     int nearestRow;           /* the row of lowest squared distance over all rows (lowest row on ties) */
     float nearestDistance;    /* sqrtf of that squared distance */
 } sbmp_goal_answer;
+/* A masked query (sbmp_kgmt_query_goals_alive, sbmp_tree_query_alive_batch) skips a row iff its
+ * alive byte is 0 (any non-zero byte is alive) and answers over the rest, row numbers the
+ * tree's own.  With no alive row: count 0, firstRow -1, bestRow -1, bestCost 0, nearestRow -1,
+ * nearestDistance +inf. */
 /* out[i] answers goals[i] over the rows [0, min(treeSize, maxTreeSize)) after everything
  * enqueued has finished: exactly the rows sbmp_kgmt_copy_tree exports, the root included
  * (firstRow equals the plan's goalIndex whenever the root lies outside the disc).  One pass
@@ -296,7 +300,8 @@ typedef struct sbmp_tree_recheck {
 sbmp_status sbmp_kgmt_recheck_tree(sbmp_kgmt* h, const float* d_obstacles, int obstaclesCount, uint8_t* status,
                                    int capacity, sbmp_tree_recheck* out);
 /* sbmp_kgmt_query_goals with every row that is not alive treated as absent (count, firstRow,
- * bestRow and nearestRow alike; row numbers are the tree's own).  SBMP_ERR_STATE without a
+ * bestRow and nearestRow alike; row numbers are the tree's own): the rule at sbmp_goal_answer,
+ * over the re-check's mask, whose bytes are 0 and 1 and whose root is alive.  SBMP_ERR_STATE without a
  * re-check since the last begin(), or when min(treeSize, maxTreeSize) no longer equals the
  * re-check's rows (the tree grew: re-check again). */
 sbmp_status sbmp_kgmt_query_goals_alive(sbmp_kgmt* h, const sbmp_goal_query* goals, int count,
@@ -452,6 +457,18 @@ sbmp_status sbmp_tree_query_batch(const float* d_state, const float* d_ctrl, lon
                                   void* stream /* hipStream_t; NULL: default */);
 sbmp_status sbmp_tree_query_batch_host(const float* state, const float* ctrl, long long rows,
                                        const sbmp_goal_query* goals, int count, sbmp_goal_answer* out);
+/* sbmp_tree_query_alive_batch: the masked query of sbmp_kgmt_query_goals_alive (k_tree_query_alive)
+ * over caller rows and a caller mask: d_alive holds rows bytes in device memory, and a row is
+ * skipped iff its byte is 0 (the rule and the answer over an empty set: sbmp_goal_answer).
+ * Everything else, errors included, as sbmp_tree_query_batch; a NULL mask:
+ * SBMP_ERR_INVALID_ARGUMENT.  sbmp_tree_query_alive_batch_host is the plain loop of
+ * sbmp_tree_query_batch_host with that one test in front, over host rows and a host mask. */
+sbmp_status sbmp_tree_query_alive_batch(const float* d_state, const float* d_ctrl, const uint8_t* d_alive,
+                                        long long rows, const sbmp_goal_query* goals, int count,
+                                        sbmp_goal_answer* out, void* stream /* hipStream_t; NULL: default */);
+sbmp_status sbmp_tree_query_alive_batch_host(const float* state, const float* ctrl, const uint8_t* alive,
+                                             long long rows, const sbmp_goal_query* goals, int count,
+                                             sbmp_goal_answer* out);
 /* sbmp_tree_recheck_batch: the re-check of sbmp_kgmt_recheck_tree (k_tree_recheck, k_tree_alive)
  * over caller rows in the planner's tree layout: state rows x 4 floats (x, y, theta, v), ctrl
  * rows x 4 floats (a, steering, duration, -; a point agent: vx, vy, duration, -), parent rows

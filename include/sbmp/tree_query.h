@@ -30,10 +30,21 @@
 // toward the lowest row.  A minimum of keys does not depend on the order the rows arrive
 // in, so the answer is the same bits on every run.  (A NaN d2 or cost, which no tree row
 // holds, orders by its bit pattern, above +inf.)
+//
+// The masked query (k_tree_query_alive, sbmp_tree_query_alive_batch, sbmp_kgmt_query_goals_alive)
+// takes one byte per row beside the rows:
+//     a row is skipped iff its alive byte is 0; any non-zero byte is alive
+//     the rows that remain answer as above, and row numbers stay the tree's own
+//     with no alive row the answer is count 0, firstRow -1, bestRow -1, bestCost 0,
+//     nearestRow -1, nearestDistance +inf
+// The last case is kNoGoalKey left in the nearest key: no row produces that key, because rows
+// are below 2^31.  The re-check (tree_recheck.h) writes only 0 and 1, and its root is always
+// alive; a caller's mask need not be either.
 #pragma once
 
 #include <stdint.h>
 
+#include "sbmp/sbmp.h"
 #include "sbmp/sbmp_math.h"
 
 #if defined(__clang__)
@@ -67,6 +78,49 @@ static inline float goal_radius_threshold(float r) {
         else hi = mid;
     }
     return u2f(lo);
+}
+
+// The answer of one goal from its accumulators: the inside rows' count, the lowest of them
+// (~0u if none), the lowest goal_key(cost, row) among them and the lowest goal_key(d2, row)
+// over every row that was not skipped (kNoGoalKey if there was none).  Host only.
+static inline sbmp_goal_answer goal_answer_of(unsigned count, unsigned first, unsigned long long best,
+                                              unsigned long long nearest) {
+    sbmp_goal_answer a;
+    a.count = (int)count;
+    a.firstRow = count ? (int)first : -1;
+    a.bestRow = count ? (int)(uint32_t)best : -1;
+    a.bestCost = count ? u2f((uint32_t)(best >> 32)) : 0.0f;
+    if (nearest == kNoGoalKey) {   // every row was skipped
+        a.nearestRow = -1;
+        a.nearestDistance = u2f(0x7f800000u);   // +inf
+    } else {
+        a.nearestRow = (int)(uint32_t)nearest;
+        a.nearestDistance = __builtin_sqrtf(u2f((uint32_t)(nearest >> 32)));
+    }
+    return a;
+}
+
+// The literal rule over host rows, row by row (no threshold): what the kernels must reproduce.
+// state, ctrl: rows x 4 floats, (x, y, -, -) and (-, -, -, cost); alive: rows bytes, or null
+// for the unmasked query.
+static inline void query_rows_host(const float* state, const float* ctrl, const uint8_t* alive, long long rows,
+                                   const sbmp_goal_query* goals, int count, sbmp_goal_answer* out) {
+    for (int i = 0; i < count; ++i) {
+        unsigned n = 0u, first = ~0u;
+        unsigned long long best = kNoGoalKey, nearest = kNoGoalKey;
+        for (long long row = 0; row < rows; ++row) {
+            if (alive && alive[row] == 0) continue;
+            const float d2 = goal_d2(state[4 * row], state[4 * row + 1], goals[i].x, goals[i].y);
+            const unsigned long long nk = goal_key(d2, (uint32_t)row);
+            if (nk < nearest) nearest = nk;
+            if (!goal_inside(d2, goals[i].radius)) continue;
+            ++n;
+            if ((unsigned)row < first) first = (unsigned)row;
+            const unsigned long long bk = goal_key(ctrl[4 * row + 3], (uint32_t)row);
+            if (bk < best) best = bk;
+        }
+        out[i] = goal_answer_of(n, first, best, nearest);
+    }
 }
 
 }  // namespace sbmp

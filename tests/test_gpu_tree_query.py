@@ -1,22 +1,29 @@
-"""GPU: k_tree_query (goal queries against tree rows, include/sbmp/tree_query.h).
+"""GPU: k_tree_query and k_tree_query_alive (goal queries against tree rows, include/sbmp/tree_query.h).
 
 Step level: sbmp_tree_query_batch on the crafted rows of tests/tree_query_cases.py against the
 numpy model (tests/tree_query_model.py) and against the host twin, which applies the literal
-sqrtf(d2) < r rule where the kernel compares d2 with a threshold.  Planner level:
-KGMT.query_goals against the model over KGMT.tree(), after plan(), between steps, on a local
-shard group and on a batch member.  Every comparison is bit-exact.
+sqrtf(d2) < r rule where the kernel compares d2 with a threshold; sbmp_tree_query_alive_batch
+on the masked cases in the same way, against the model over the alive rows and the masked host
+twin.  Planner level: KGMT.query_goals against the model over KGMT.tree(), after plan(), between
+steps, on a local shard group and on a batch member, and KGMT.query_goals(alive=True) against
+the step-level masked entry over the same tree.  Every comparison is bit-exact.
 
-The kernel takes 2,048 rows per workgroup and step on a grid of at most 8 workgroups per CU:
+k_tree_query takes 2,048 rows per workgroup and step on a grid of at most 8 workgroups per CU:
 one sweep is at most 4,194,304 rows on the 256 CUs of an MI355X, and the case single-4194381
-goes round the grid-stride loop a second time.
+goes round the grid-stride loop a second time.  k_tree_query_alive takes 256 rows per workgroup
+and sweep on a grid of the same bound: one sweep is at most 524,288 rows, and masked-rows-524365
+and masked-rows-1048577 hold alive inside rows, and the nearest row, in its second and third
+sweep (with fewer resident workgroups the sweeps are shorter and those rows lie in later ones).
 """
 import numpy as np
 import pytest
 
 from conftest import DEMO, DEMO_GOAL, DEMO_INITIAL, bits
 from scenarios import BASE, BASE_SEED
-from tree_query_cases import NAMES, case, check_expect
+from scenarios import random_boxes
+from tree_query_cases import MASKED_NAMES, NAMES, case, check_expect, masked_case
 from tree_query_model import FIELDS, assert_same_answers, model_of_rows, tree_rows
+from tree_recheck_model import tree_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -88,7 +95,70 @@ def test_radius_argument_forms():
     assert_same_answers(tree_query_batch(state, ctrl, one[:, :2], 1.25), tree_query_batch(state, ctrl, one))
 
 
+# ---------------------------------------------------------------- step level, masked
+@pytest.mark.parametrize("name", MASKED_NAMES)
+def test_masked_device_matches_model_and_host(name):
+    from cudasbmp_amd import tree_query_batch
+    c = masked_case(name)   # where the mask must matter is asserted as the case is built
+    dev = tree_query_batch(c.state, c.ctrl, c.goals, alive=c.mask)
+    assert_same_answers(dev, c.model, label=f"{name} device vs model")
+    host = tree_query_batch(c.state, c.ctrl, c.goals, alive=c.mask, device=False)
+    assert_same_answers(dev, host, label=f"{name} device vs host")
+    check_expect(dev, c.expect, label=name)
+
+
+@pytest.mark.parametrize("name", ["masked-ties", "masked-goals-65", "masked-none"])
+def test_two_masked_launches_give_identical_bytes(name):
+    from cudasbmp_amd import tree_query_batch
+    c = masked_case(name)
+    a = tree_query_batch(c.state, c.ctrl, c.goals, alive=c.mask)
+    b = tree_query_batch(c.state, c.ctrl, c.goals, alive=c.mask)
+    for k in FIELDS:
+        assert a[k].tobytes() == b[k].tobytes(), k
+
+
+def test_any_nonzero_byte_is_alive():
+    from cudasbmp_amd import tree_query_batch
+    b, z = masked_case("masked-bytes"), masked_case("masked-bytes-01")
+    assert np.array_equal(b.mask != 0, z.mask == 1) and ((b.mask & 1) == 0).sum() > 1000
+    got = tree_query_batch(b.state, b.ctrl, b.goals, alive=b.mask)
+    assert_same_answers(got, tree_query_batch(z.state, z.ctrl, z.goals, alive=z.mask), label="bytes vs 0 / 1")
+    assert_same_answers(got, z.model, label="bytes vs the 0 / 1 model")
+
+
+@pytest.mark.parametrize("name", ["ties", "radius-edges", "degenerate", "overflow", "random"])
+def test_a_mask_of_ones_gives_the_unmasked_answers(name):
+    from cudasbmp_amd import tree_query_batch
+    state, ctrl, goals, expect, model = case(name)
+    unmasked = tree_query_batch(state, ctrl, goals)
+    for byte in (1, 0xff):
+        got = tree_query_batch(state, ctrl, goals, alive=np.full(len(state), byte, np.uint8))
+        assert_same_answers(got, unmasked, label=f"{name} masked kernel vs unmasked kernel")
+        assert_same_answers(got, model, label=f"{name} masked kernel vs model")
+        check_expect(got, expect, label=name)
+
+
 # ---------------------------------------------------------------- planner level
+def test_planner_masked_query_equals_the_step_level_entry(obstacles):
+    """After recheck(), query_goals(alive=True) is sbmp_tree_query_alive_batch over tree() and the
+    mask status == 0 (FREE and not CUT: alive)."""
+    from cudasbmp_amd import tree_query_batch
+    g = _mk(**BASE)
+    g.plan(DEMO_INITIAL, DEMO_GOAL, _dev(obstacles), len(obstacles), seed=BASE_SEED)
+    other = random_boxes(600, 20.0, 20.0, 7, 0.3, 0.8)
+    status, summary = g.recheck(other)
+    s, p, c = g.tree()
+    state, ctrl, parent = tree_arrays(s, p, c, g.result().treeSize)
+    alive = status == 0
+    assert len(alive) == len(state) and 1 < summary["alive"] == alive.sum() < len(alive)
+    goals = np.concatenate([_workspace_goals(), np.full((67, 1), 0.5, np.float32)], axis=1)
+    got = g.query_goals(goals, alive=True)
+    assert_same_answers(got, tree_query_batch(state, ctrl, goals, alive=alive), label="planner vs step level")
+    assert_same_answers(got, model_of_rows(state, ctrl, goals, alive), label="planner vs model")
+    assert (got["count"] > 0).any() and (got["count"] == 0).any()
+    assert got["count"].tobytes() != g.query_goals(goals)["count"].tobytes()   # the mask matters
+
+
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_query_of_the_plans_own_goal(seed, obstacles):
     g = _mk()

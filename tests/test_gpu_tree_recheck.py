@@ -69,11 +69,7 @@ def _model_of_tree(g, boxes):
 
 def _alive_answers(state, ctrl, alive, goals):
     """tests/tree_query_model.py over the alive rows only, row numbers mapped back to the tree's."""
-    idx = np.flatnonzero(alive)
-    m = model_of_rows(state[idx], ctrl[idx], goals)
-    for k in ("firstRow", "bestRow", "nearestRow"):
-        m[k] = np.where(m[k] >= 0, idx[np.maximum(m[k], 0)], -1).astype(np.int32)
-    return m
+    return model_of_rows(state, ctrl, goals, alive)
 
 
 # ---------------------------------------------------------------- step level

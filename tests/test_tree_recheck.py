@@ -152,7 +152,7 @@ def test_library_exports_the_recheck_symbols():
     from cudasbmp_amd import _native as nat
     L = nat.lib()
     for f in ("sbmp_kgmt_recheck_tree", "sbmp_kgmt_query_goals_alive", "sbmp_tree_recheck_batch",
-              "sbmp_tree_recheck_batch_host"):
+              "sbmp_tree_recheck_batch_host", "sbmp_tree_query_alive_batch", "sbmp_tree_query_alive_batch_host"):
         assert hasattr(L, f) and f in nat.EXPORTED_SYMBOLS
     assert ctypes.sizeof(nat.TreeRecheck) == 28
     assert (nat.SBMP_ROW_FREE, nat.SBMP_ROW_ORPHAN, nat.SBMP_ROW_BLOCKED, nat.SBMP_ROW_STALE, nat.SBMP_ROW_CUT) == \
