@@ -158,6 +158,7 @@ EXPORTED_SYMBOLS = (
     "sbmp_kgmt_solution_paths", "sbmp_kgmt_trace_rows", "sbmp_tree_paths_batch", "sbmp_tree_paths_batch_host",
     "sbmp_tree_trace_batch", "sbmp_tree_trace_batch_host",
     "sbmp_tree_query_alive_batch", "sbmp_tree_query_alive_batch_host",
+    "sbmp_kgmt_resample_paths", "sbmp_tree_resample_batch", "sbmp_tree_resample_batch_host",
 )
 
 _lib = None
@@ -259,6 +260,12 @@ def lib():
                                        P(ctypes.c_longlong)],
         "sbmp_tree_trace_batch": [P(TreePathsArgs), vp, ctypes.c_longlong, vp, vp, vp],
         "sbmp_tree_trace_batch_host": [P(TreePathsArgs), vp, ctypes.c_longlong, vp, vp],
+        "sbmp_kgmt_resample_paths": [vp, vp, i, ctypes.c_double, vp, vp, vp, vp, vp, ctypes.c_longlong,
+                                     P(ctypes.c_longlong)],
+        "sbmp_tree_resample_batch": [P(TreePathsArgs), vp, i, ctypes.c_double, vp, vp, vp, vp, vp, ctypes.c_longlong,
+                                     P(ctypes.c_longlong), vp],
+        "sbmp_tree_resample_batch_host": [P(TreePathsArgs), vp, i, ctypes.c_double, vp, vp, vp, vp, vp,
+                                          ctypes.c_longlong, P(ctypes.c_longlong)],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -1245,6 +1245,20 @@ void KgmtPlanner::trace_rows(const int* rows, long long count, float* steps, uin
     tree_trace_to_host(d_, p_.agent, R, rows, count, steps, status, stream_);
 }
 
+// Paths on one clock (tree_resample.hip): as solution_paths, behind everything enqueued, reading
+// the tree only, into buffers of the call's own.
+void KgmtPlanner::resample_paths(const int* nodes, int count, double period, int* counts, uint8_t* status,
+                                 float* states, int* edges, double* times, long long capacity, long long* total) {
+    if (!total) throw Error(SBMP_ERR_INVALID_ARGUMENT, "total must be non-NULL");
+    *total = 0;
+    if (count < 0 || (count > 0 && !nodes)) throw Error(SBMP_ERR_INVALID_ARGUMENT, "bad node list");
+    const int R = settled_rows(count > 0);
+    tree_resample_check(nodes, count, R, period, total);
+    if (count == 0) return;
+    tree_resample_device(d_, p_.agent, R, p_.numIterations + 2, nodes, count, period, counts, status, states, edges,
+                         times, false, capacity, total, stream_);
+}
+
 unsigned long long* KgmtPlanner::alloc_scratch_u64() {
     if (!scratch_) scratch_ = alloc<unsigned long long>(8);
     return scratch_;

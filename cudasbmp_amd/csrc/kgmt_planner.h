@@ -99,6 +99,11 @@ public:
     virtual void solution_paths(const int* nodes, int count, int* lengths, uint8_t* status, int* rows, float* samples,
                                 float* costs, long long capacity, long long* total) = 0;
     virtual void trace_rows(const int* rows, long long count, float* steps, uint8_t* status) = 0;
+    // The paths of `count` nodes resampled every `period` seconds (k_resample_clock,
+    // k_path_resample; include/sbmp/tree_resample.h), as sbmp_kgmt_resample_paths takes them.
+    // Reads the tree only.
+    virtual void resample_paths(const int* nodes, int count, double period, int* counts, uint8_t* status, float* states,
+                                int* edges, double* times, long long capacity, long long* total) = 0;
     void export_csv(const std::string& dir);
 
     virtual std::vector<sbmp_kernel_stat> kernel_stats() = 0;
@@ -165,6 +170,29 @@ void tree_trace_batch(const sbmp_tree_paths_args* a, const int* d_rows, long lon
                       uint8_t* d_status, hipStream_t stream);
 void tree_trace_batch_host(const sbmp_tree_paths_args* a, const int* rows, long long count, float* steps,
                            uint8_t* status);
+// k_path_walk's two passes over device arrays, queued on `stream` without a wait (tree_paths.hip):
+// pass A writes d_len and d_status, pass B the rows / samples / costs that are non-null at the
+// 64-bit row offsets d_off.
+void path_walk_lengths_device(const KgmtDev& d, int depthBound, const int* d_nodes, int count, int* d_len,
+                              uint8_t* d_status, hipStream_t stream);
+void path_walk_rows_device(const KgmtDev& d, int depthBound, const int* d_nodes, int count, int* d_len,
+                           uint8_t* d_status, const long long* d_off, int* d_rows, float* d_samples, float* d_costs,
+                           hipStream_t stream);
+
+// Paths resampled at a fixed period (tree_resample.hip; include/sbmp/tree_resample.h).  d: the tree
+// pointers, numDisc / agentLength and their reciprocals.  nodes, counts and status are host memory;
+// states / edges / times are host memory, or device memory with deviceOut set.  *total is set
+// before a capacity error.  Runs on `stream` and waits for the result; scratch is per call.
+void tree_resample_check(const int* nodes, int count, int rows, double period, const long long* total);
+void tree_resample_device(const KgmtDev& d, int agent, int rows, int depthBound, const int* nodes, int count,
+                          double period, int* counts, uint8_t* status, float* states, int* edges, double* times,
+                          bool deviceOut, long long capacity, long long* total, hipStream_t stream);
+void tree_resample_batch(const sbmp_tree_paths_args* a, const int* nodes, int count, double period, int* counts,
+                         uint8_t* status, float* d_states, int* d_edges, double* d_times, long long capacity,
+                         long long* total, hipStream_t stream);
+void tree_resample_batch_host(const sbmp_tree_paths_args* a, const int* nodes, int count, double period, int* counts,
+                              uint8_t* status, float* states, int* edges, double* times, long long capacity,
+                              long long* total);
 
 // Times kernel launches of `ids` kinds with event pairs: the pairs are handed to
 // hipExtLaunchKernelGGL, which stamps them with the kernel's own start/end.
@@ -257,6 +285,8 @@ public:
     void solution_paths(const int* nodes, int count, int* lengths, uint8_t* status, int* rows, float* samples,
                         float* costs, long long capacity, long long* total) override;
     void trace_rows(const int* rows, long long count, float* steps, uint8_t* status) override;
+    void resample_paths(const int* nodes, int count, double period, int* counts, uint8_t* status, float* states,
+                        int* edges, double* times, long long capacity, long long* total) override;
 
     std::vector<sbmp_kernel_stat> kernel_stats() override;
     void path_info(sbmp_path_info* out) override;
@@ -419,6 +449,11 @@ public:
     void trace_rows(const int* rows, long long count, float* steps, uint8_t* status) override {
         sync();
         r0().trace_rows(rows, count, steps, status);
+    }
+    void resample_paths(const int* nodes, int count, double period, int* counts, uint8_t* status, float* states,
+                        int* edges, double* times, long long capacity, long long* total) override {
+        sync();
+        r0().resample_paths(nodes, count, period, counts, status, states, edges, times, capacity, total);
     }
 
     std::vector<sbmp_kernel_stat> kernel_stats() override { return r0().kernel_stats(); }

@@ -254,6 +254,23 @@ sbmp_status sbmp_tree_trace_batch_host(const sbmp_tree_paths_args* args, const i
     return guarded([&] { sbmp::tree_trace_batch_host(args, rows, count, steps, status); });
 }
 
+sbmp_status sbmp_tree_resample_batch(const sbmp_tree_paths_args* args, const int* nodes, int count, double period,
+                                     int* counts, uint8_t* status, float* d_states, int* d_edges, double* d_times,
+                                     long long capacity, long long* total, void* stream) {
+    return guarded([&] {
+        sbmp::tree_resample_batch(args, nodes, count, period, counts, status, d_states, d_edges, d_times, capacity, total,
+                                  static_cast<hipStream_t>(stream));
+    });
+}
+
+sbmp_status sbmp_tree_resample_batch_host(const sbmp_tree_paths_args* args, const int* nodes, int count, double period,
+                                          int* counts, uint8_t* status, float* states, int* edges, double* times,
+                                          long long capacity, long long* total) {
+    return guarded([&] {
+        sbmp::tree_resample_batch_host(args, nodes, count, period, counts, status, states, edges, times, capacity, total);
+    });
+}
+
 sbmp_status sbmp_goal_radius_threshold(float r, float* t) {
     return guarded([&] {
         REQUIRE(t, "t must be non-NULL");
@@ -483,6 +500,15 @@ sbmp_status sbmp_kgmt_trace_rows(sbmp_kgmt* h, const int* rows, long long count,
     return guarded([&] {
         PLANNER(h);
         P.trace_rows(rows, count, steps, status);
+    });
+}
+
+sbmp_status sbmp_kgmt_resample_paths(sbmp_kgmt* h, const int* nodes, int count, double period, int* counts,
+                                     uint8_t* status, float* states, int* edges, double* times, long long capacity,
+                                     long long* total) {
+    return guarded([&] {
+        PLANNER(h);
+        P.resample_paths(nodes, count, period, counts, status, states, edges, times, capacity, total);
     });
 }
 

@@ -193,6 +193,28 @@ void tree_paths_check(const int* nodes, int count, int rows, const long long* to
         throw Error(SBMP_ERR_INVALID_ARGUMENT, "a node is neither -1 nor a row of [0, " + std::to_string(rows) + ")");
 }
 
+// The two passes of k_path_walk over device arrays, queued on `stream` (no wait): pass A writes
+// d_len and d_status; pass B reads d_len and the 64-bit row offsets d_off and writes the rows,
+// samples and costs that are non-null.  tree_resample.hip walks its paths through them too.
+void path_walk_lengths_device(const KgmtDev& d, int depthBound, const int* d_nodes, int count, int* d_len,
+                              uint8_t* d_status, hipStream_t stream) {
+    const int grid = (count + kPathsBlock - 1) / kPathsBlock;
+    hipLaunchKernelGGL(k_path_walk<false>, dim3(grid), dim3(kPathsBlock), 0, stream, (const float4*)d.treeState,
+                       (const float4*)d.treeCtrl, (const int*)d.treeParent, depthBound, d_nodes, count, d_len, d_status,
+                       (const long long*)nullptr, (int*)nullptr, (float*)nullptr, (float*)nullptr);
+    SBMP_HIP(hipGetLastError());
+}
+
+void path_walk_rows_device(const KgmtDev& d, int depthBound, const int* d_nodes, int count, int* d_len,
+                           uint8_t* d_status, const long long* d_off, int* d_rows, float* d_samples, float* d_costs,
+                           hipStream_t stream) {
+    const int grid = (count + kPathsBlock - 1) / kPathsBlock;
+    hipLaunchKernelGGL(k_path_walk<true>, dim3(grid), dim3(kPathsBlock), 0, stream, (const float4*)d.treeState,
+                       (const float4*)d.treeCtrl, (const int*)d.treeParent, depthBound, d_nodes, count, d_len, d_status,
+                       d_off, d_rows, d_samples, d_costs);
+    SBMP_HIP(hipGetLastError());
+}
+
 void tree_paths_device(const KgmtDev& d, int rows, int depthBound, const int* nodes, int count, int* lengths,
                        uint8_t* status, int* outRows, float* samples, float* costs, long long capacity,
                        long long* total, hipStream_t stream) {
@@ -205,12 +227,8 @@ void tree_paths_device(const KgmtDev& d, int rows, int depthBound, const int* no
         int* dLen = w.alloc<int>(count);
         uint8_t* dStatus = w.alloc<uint8_t>(count);
         std::vector<int> hLen(count);
-        const int grid = (count + kPathsBlock - 1) / kPathsBlock;
         SBMP_HIP(hipMemcpyAsync(dNodes, nodes, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(k_path_walk<false>, dim3(grid), dim3(kPathsBlock), 0, stream, (const float4*)d.treeState,
-                           (const float4*)d.treeCtrl, (const int*)d.treeParent, depthBound, (const int*)dNodes, count,
-                           dLen, dStatus, (const long long*)nullptr, (int*)nullptr, (float*)nullptr, (float*)nullptr);
-        SBMP_HIP(hipGetLastError());
+        path_walk_lengths_device(d, depthBound, dNodes, count, dLen, dStatus, stream);
         read_back(stream, {{hLen.data(), dLen, sizeof(int) * (size_t)count}, {status, dStatus, (size_t)count}});
         std::vector<long long> off(count);
         long long sum = 0;
@@ -230,10 +248,7 @@ void tree_paths_device(const KgmtDev& d, int rows, int depthBound, const int* no
         float* dSamples = samples ? w.alloc<float>(7 * (size_t)sum) : nullptr;
         float* dCosts = costs ? w.alloc<float>((size_t)sum) : nullptr;
         SBMP_HIP(hipMemcpyAsync(dOff, off.data(), sizeof(long long) * (size_t)count, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(k_path_walk<true>, dim3(grid), dim3(kPathsBlock), 0, stream, (const float4*)d.treeState,
-                           (const float4*)d.treeCtrl, (const int*)d.treeParent, depthBound, (const int*)dNodes, count,
-                           dLen, dStatus, (const long long*)dOff, dRows, dSamples, dCosts);
-        SBMP_HIP(hipGetLastError());
+        path_walk_rows_device(d, depthBound, dNodes, count, dLen, dStatus, dOff, dRows, dSamples, dCosts, stream);
         read_back(stream, {{outRows, dRows, sizeof(int) * (size_t)sum},
                            {samples, dSamples, sizeof(float) * 7 * (size_t)sum},
                            {costs, dCosts, sizeof(float) * (size_t)sum}});

@@ -317,6 +317,20 @@ class KGMT:
         out["steps"], out["step_status"] = self.trace(out["rows"])
         return out
 
+    def resample(self, nodes, period) -> dict:
+        """The paths root .. node of many nodes as set-points on one clock, one every `period`
+        seconds of path time from the root, in one device pass (sbmp_kgmt_resample_paths;
+        include/sbmp/tree_resample.h).  Every set-point lies on the Euler segment the planner
+        collision-checked; the last sample of a path is the node as stored, at the path's total
+        time.  Returns counts (Q,), status (Q,) of SBMP_PATH_*, offsets (Q + 1, int64), states
+        (total, 4) of (x, y, theta, v), edges (total,) (the row whose edge a sample lies on) and
+        times (total,) float64; path i is [offsets[i], offsets[i + 1])."""
+        from .tree_resample import resample_dict
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).ravel()
+        n = nodes.ctypes.data_as(ctypes.c_void_p) if len(nodes) else None
+        return resample_dict(lambda *o: nat.call("sbmp_kgmt_resample_paths", self._h, n, len(nodes),
+                                                 ctypes.c_double(float(period)), *o), nodes)
+
     def query_goals(self, goals, radius=None, alive: bool = False) -> dict:
         """Goal discs against the tree as it stands (sbmp_kgmt_query_goals; one k_tree_query pass
         per 16 goals): goals is (Q, 2) with one radius for all, or (Q, 3) rows of (x, y, radius).

@@ -154,6 +154,15 @@ public:
     void traceRows(const std::vector<int>& rows, std::vector<float>& steps, std::vector<uint8_t>& status) const {
         traceRowsOf(h_, numDisc_, rows, steps, status);
     }
+    // The paths of many nodes as set-points on one clock, one every `period` seconds of path time
+    // from the root, in one device pass (sbmp_kgmt_resample_paths; sbmp/tree_resample.h): counts and
+    // status (SBMP_PATH_*) per request; states (4 floats per sample), edges and times hold the paths
+    // one behind the other, path i at the sum of counts[0 .. i).  Returns the number of samples.
+    long long resamplePaths(const std::vector<int>& nodes, double period, std::vector<int>& counts,
+                            std::vector<uint8_t>& status, std::vector<float>& states, std::vector<int>& edges,
+                            std::vector<double>& times) const {
+        return resamplePathsOf(h_, nodes, period, counts, status, states, edges, times);
+    }
     // The two calls on any planner handle (KGMTBatch passes a member's).
     static long long solutionPathsOf(sbmp_kgmt* h, const std::vector<int>& nodes, std::vector<int>& lengths,
                                      std::vector<uint8_t>& status, std::vector<int>& rows, std::vector<float>& samples,
@@ -170,6 +179,23 @@ public:
         if (total)
             SBMP_CHECK(sbmp_kgmt_solution_paths(h, nodes.data(), count, lengths.data(), status.data(), rows.data(),
                                                 samples.data(), costs ? costs->data() : nullptr, total, &total));
+        return total;
+    }
+    static long long resamplePathsOf(sbmp_kgmt* h, const std::vector<int>& nodes, double period, std::vector<int>& counts,
+                                     std::vector<uint8_t>& status, std::vector<float>& states, std::vector<int>& edges,
+                                     std::vector<double>& times) {
+        const int count = (int)nodes.size();
+        long long total = 0;
+        counts.assign(nodes.size(), 0);
+        status.assign(nodes.size(), 0);
+        SBMP_CHECK(sbmp_kgmt_resample_paths(h, nodes.data(), count, period, counts.data(), status.data(), nullptr,
+                                            nullptr, nullptr, 0, &total));
+        states.assign(4 * (size_t)total, 0.0f);
+        edges.assign((size_t)total, 0);
+        times.assign((size_t)total, 0.0);
+        if (total)
+            SBMP_CHECK(sbmp_kgmt_resample_paths(h, nodes.data(), count, period, counts.data(), status.data(),
+                                                states.data(), edges.data(), times.data(), total, &total));
         return total;
     }
     static void traceRowsOf(sbmp_kgmt* h, int numDisc, const std::vector<int>& rows, std::vector<float>& steps,

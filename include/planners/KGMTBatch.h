@@ -106,6 +106,12 @@ public:
     void traceRows(int i, const std::vector<int>& rows, std::vector<float>& steps, std::vector<uint8_t>& status) const {
         KGMT::traceRowsOf(member(i), params_.numDisc, rows, steps, status);
     }
+    // Member i's paths on one clock (KGMT::resamplePaths).
+    long long resamplePaths(int i, const std::vector<int>& nodes, double period, std::vector<int>& counts,
+                            std::vector<uint8_t>& status, std::vector<float>& states, std::vector<int>& edges,
+                            std::vector<double>& times) const {
+        return KGMT::resamplePathsOf(member(i), nodes, period, counts, status, states, edges, times);
+    }
     sbmp_kgmt_batch* handle() const { return h_; }
 
 private:

@@ -341,6 +341,23 @@ sbmp_status sbmp_kgmt_solution_paths(sbmp_kgmt* h, const int* nodes, int count, 
  * rows NULL with count > R: SBMP_ERR_INVALID_ARGUMENT.  count == 0 is a no-op; otherwise 0 <
  * count < 2^31.  State, waiting and handles as sbmp_kgmt_solution_paths (k_tree_trace). */
 sbmp_status sbmp_kgmt_trace_rows(sbmp_kgmt* h, const int* rows, long long count, float* steps, uint8_t* status);
+/* The paths of `count` nodes resampled on one clock in one device pass (include/sbmp/tree_resample.h
+ * states the rule): set-points every `period` seconds of path time from the
+ * root, each on the Euler segment the planner collision-checked, plus the node itself as the
+ * last sample.  nodes, statuses, state, waiting and handles as sbmp_kgmt_solution_paths; a
+ * request whose status is not SBMP_PATH_OK gets 0 samples.  counts (ints) and status (bytes):
+ * count entries each, may be NULL.  Path i of total time T has floor(T / period) + 2 samples,
+ * at the exclusive sum of counts[0 .. i): states (4 floats: x, y, theta, v), edges (the row
+ * whose edge the sample lies on; the node for the last sample) and times (doubles, seconds from
+ * the root; T for the last sample); each may be NULL, capacity = their length in samples.
+ * *total = the sum of the counts, set in every case: with capacity < *total and any of the
+ * three given the call fails with SBMP_ERR_INVALID_ARGUMENT, so a NULL / 0 call returns the
+ * size to allocate.  period not finite or <= 0, or a path with T / period >= 2^31 - 2:
+ * SBMP_ERR_INVALID_ARGUMENT.  Only reads the tree (k_path_walk, k_resample_clock,
+ * k_path_resample on the planner's stream over buffers of the call's own). */
+sbmp_status sbmp_kgmt_resample_paths(sbmp_kgmt* h, const int* nodes, int count, double period, int* counts,
+                                     uint8_t* status, float* states, int* edges, double* times, long long capacity,
+                                     long long* total);
 
 sbmp_status sbmp_kgmt_kernel_stats(sbmp_kgmt* h, sbmp_kernel_stat* out, int capacity, int* count);
 /* The form of the hot path chosen at the last begin() (sbmp_path_info). */
@@ -528,6 +545,17 @@ sbmp_status sbmp_tree_trace_batch(const sbmp_tree_paths_args* args, const int* d
                                   float* d_steps, uint8_t* d_status, void* stream /* hipStream_t; NULL: default */);
 sbmp_status sbmp_tree_trace_batch_host(const sbmp_tree_paths_args* args, const int* rows, long long count,
                                        float* steps, uint8_t* status);
+/* sbmp_kgmt_resample_paths over caller rows (args as above; agent, numDisc and agentLength
+ * are read).  nodes, counts and status are host arrays; d_states, d_edges and d_times are device
+ * memory, so the result can stay on the device.  Waits for the result.  The _host twin takes
+ * every array in host memory and applies the literal rule in plain loops (resample_paths_host of
+ * include/sbmp/tree_resample.h); it needs no device. */
+sbmp_status sbmp_tree_resample_batch(const sbmp_tree_paths_args* args, const int* nodes, int count, double period,
+                                     int* counts, uint8_t* status, float* d_states, int* d_edges, double* d_times,
+                                     long long capacity, long long* total, void* stream /* hipStream_t; NULL: default */);
+sbmp_status sbmp_tree_resample_batch_host(const sbmp_tree_paths_args* args, const int* nodes, int count, double period,
+                                          int* counts, uint8_t* status, float* states, int* edges, double* times,
+                                          long long capacity, long long* total);
 
 /* The threshold the kernel compares d2 with (host-only, no device needed): *t = the largest
  * float d2 with sqrtf(d2) < r, found by bisecting the float bit patterns with that rule;
@@ -608,7 +636,7 @@ sbmp_status sbmp_kgmt_batch_enqueue(sbmp_kgmt_batch* h, int iterations);
 sbmp_status sbmp_kgmt_batch_sync(sbmp_kgmt_batch* h);
 sbmp_status sbmp_kgmt_batch_result(sbmp_kgmt_batch* h, int member, sbmp_plan_result* result);
 /* Member i as a planner handle owned by the batch, for every read-only call above
- * (copy_tree, copy_regions, copy_rng, iter_log, solution_path, solution_paths, trace_rows, query_goals, recheck_tree,
+ * (copy_tree, copy_regions, copy_rng, iter_log, solution_path, solution_paths, trace_rows, resample_paths, query_goals, recheck_tree,
  * query_goals_alive, state_hash,
  * export_csv, path_info, kernel_stats, ...).  sbmp_kgmt_plan / begin / step / enqueue / destroy on it fail
  * with SBMP_ERR_STATE, sbmp_kgmt_set_iteration_dump with SBMP_ERR_UNSUPPORTED. */
