@@ -131,6 +131,10 @@ class TreePathsArgs(ctypes.Structure):   # sbmp_tree_paths_args
 SBMP_PATH_OK, SBMP_PATH_NONE, SBMP_PATH_BROKEN, SBMP_PATH_DEEP = 0, 1, 2, 3
 
 
+class FoldInfo(ctypes.Structure):   # sbmp_fold_info
+    _fields_ = [(n, ctypes.c_int) for n in ("window", "keysPerGroup", "maxR2", "maxRanks", "groups", "per")]
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", ctypes.c_longlong), ("totalMs", ctypes.c_double)]
 
@@ -159,6 +163,7 @@ EXPORTED_SYMBOLS = (
     "sbmp_tree_trace_batch", "sbmp_tree_trace_batch_host",
     "sbmp_tree_query_alive_batch", "sbmp_tree_query_alive_batch_host",
     "sbmp_kgmt_resample_paths", "sbmp_tree_resample_batch", "sbmp_tree_resample_batch_host",
+    "sbmp_fold_r2_info", "sbmp_fold_r2_batch", "sbmp_fold_r2_batch_host",
 )
 
 _lib = None
@@ -266,6 +271,9 @@ def lib():
                                      P(ctypes.c_longlong), vp],
         "sbmp_tree_resample_batch_host": [P(TreePathsArgs), vp, i, ctypes.c_double, vp, vp, vp, vp, vp,
                                           ctypes.c_longlong, P(ctypes.c_longlong)],
+        "sbmp_fold_r2_info": [i, P(FoldInfo)],
+        "sbmp_fold_r2_batch": [vp, vp, vp, i, i, i, i, i, i, vp, vp, vp],
+        "sbmp_fold_r2_batch_host": [vp, vp, vp, i, i, i, i, i, i, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -2282,10 +2282,8 @@ void launch_fold_r2(const KgmtDev& d, int tFirst, int tLast, hipStream_t s, cons
     if (shm > 65536)   // dynamic LDS above 64 KB needs the opt-in; per device, so every time
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fold_r2),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    // the iteration's keys split evenly (whole 8-key loads) over the fewest workgroups of
-    // at most kFoldKeys each
-    const int groups = (d.logSlots + kFoldKeys - 1) / kFoldKeys;
-    const int per = (((d.logSlots + groups - 1) / groups) + 7) & ~7;
+    int groups, per;
+    fold_split(d.logSlots, &groups, &per);
     const dim3 grid(groups, tLast - tFirst + 1);
     launch(k_fold_r2, grid, dim3(kFoldThreads), shm, s, tm, d, tFirst, per);
 }

@@ -72,6 +72,12 @@ void step_batch_record(const KgmtDev& d, StepBatchRec* r);
 void launch_step_batch(const KgmtDev& d, int t, int expand, int agent, int variant, const StepBatchRec* table,
                        int members, int maxGroups, hipStream_t s, const KernelTiming& tm = KernelTiming());
 void launch_fold_r2(const KgmtDev& d, int tFirst, int tLast, hipStream_t s, const KernelTiming& tm = KernelTiming());
+// launch_fold_r2's split of a log row: the iteration's keys go evenly (whole 8-key loads)
+// to the fewest workgroups of at most kFoldKeys each
+inline void fold_split(int logSlots, int* groups, int* per) {
+    *groups = (logSlots + kFoldKeys - 1) / kFoldKeys;
+    *per = (((logSlots + *groups - 1) / *groups) + 7) & ~7;
+}
 // k_finish(t): insert iteration t (insertBlocks = every global 256-slot block) +
 // prepare iteration t+1.  t = 0 prepares iteration 1 only (insertBlocks = 0).
 int finish_insert_groups(int nBlocks);   // k_finish's insert workgroups for nBlocks 256-slot blocks

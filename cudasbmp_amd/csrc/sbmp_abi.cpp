@@ -36,6 +36,11 @@ void expand_batch_host(const sbmp_expand_batch_args* args);
 void insert_batch(const sbmp_insert_batch_args* args, void* stream);
 double hbm_copy_bandwidth(size_t bytes, int reps);
 void load_system_config(const char* path, sbmp_system_config* out);   // config.cpp
+void fold_r2_info(int logSlots, sbmp_fold_info* out);   // fold_batch.cpp
+void fold_r2_batch(const uint16_t* d_ring, const int* S, const int* executed, int tFirst, int tLast, int logSlots,
+                   int nR2, int rank, int nranks, int* d_valid, int* d_invalid, hipStream_t s);
+void fold_r2_batch_host(const uint16_t* ring, const int* S, const int* executed, int tFirst, int tLast, int logSlots,
+                        int nR2, int rank, int nranks, int* valid, int* invalid);
 }  // namespace sbmp
 
 static thread_local std::string g_last_error;
@@ -215,6 +220,26 @@ sbmp_status sbmp_tree_query_alive_batch_host(const float* state, const float* ct
                                              long long rows, const sbmp_goal_query* goals, int count,
                                              sbmp_goal_answer* out) {
     return guarded([&] { sbmp::tree_query_alive_host(state, ctrl, alive, rows, goals, count, out); });
+}
+
+sbmp_status sbmp_fold_r2_info(int logSlots, sbmp_fold_info* out) {
+    return guarded([&] { sbmp::fold_r2_info(logSlots, out); });
+}
+
+sbmp_status sbmp_fold_r2_batch(const uint16_t* d_ring, const int* S, const int* executed, int tFirst, int tLast,
+                               int logSlots, int nR2, int rank, int nranks, int* d_R2Valid, int* d_R2Invalid,
+                               void* stream) {
+    return guarded([&] {
+        sbmp::fold_r2_batch(d_ring, S, executed, tFirst, tLast, logSlots, nR2, rank, nranks, d_R2Valid, d_R2Invalid,
+                            static_cast<hipStream_t>(stream));
+    });
+}
+
+sbmp_status sbmp_fold_r2_batch_host(const uint16_t* ring, const int* S, const int* executed, int tFirst, int tLast,
+                                    int logSlots, int nR2, int rank, int nranks, int* R2Valid, int* R2Invalid) {
+    return guarded([&] {
+        sbmp::fold_r2_batch_host(ring, S, executed, tFirst, tLast, logSlots, nR2, rank, nranks, R2Valid, R2Invalid);
+    });
 }
 
 sbmp_status sbmp_tree_recheck_batch(const sbmp_tree_recheck_args* args, uint8_t* status, sbmp_tree_recheck* out,

@@ -462,6 +462,37 @@ typedef struct sbmp_insert_batch_args {
 } sbmp_insert_batch_args;
 sbmp_status sbmp_insert_batch(const sbmp_insert_batch_args* args, void* stream);
 
+/* sbmp_fold_r2_batch: the planner's fold of its R2 key log (k_fold_r2, through the planner's own
+ * launcher: its split into workgroups and its LDS opt-in) over a caller ring.  The rule is the
+ * host loop of include/sbmp/r2_fold.h: for every iteration t in [tFirst, tLast] with
+ * executed[t - tFirst] != 0 and every local key index i < logSlots, the key
+ * d_ring[(t % window) * logSlots + i] of global slot (rank + nranks (i / 256)) 256 + i % 256
+ * counts iff slot < S[t - tFirst] and (key & 0x7fff) < nR2; it then adds 1 to
+ * d_R2Valid[key & 0x7fff] when bit 15 is set, else to d_R2Invalid[key & 0x7fff].  The tables
+ * are in/out (nR2 ints each, device memory); 0xffff, 0x7fff and every other cell >= nR2 count
+ * nowhere.  d_ring: window x logSlots uint16 in device memory; S, executed: host arrays of
+ * tLast - tFirst + 1 ints.  Waits for the result.  SBMP_ERR_INVALID_ARGUMENT for logSlots
+ * not a positive multiple of 256, nR2 outside [1, maxR2], tLast - tFirst + 1 outside
+ * [1, window], tFirst < 0, tLast >= 2^20, nranks outside [1, maxRanks], rank outside [0, nranks), a NULL
+ * buffer.  sbmp_fold_r2_batch_host is that header's loop over host arrays.
+ * sbmp_fold_r2_info gives the constants and, for a logSlots (a positive multiple of 256),
+ * the launcher's split: `groups` workgroups per iteration, workgroup g taking the keys
+ * [g per, min((g + 1) per, logSlots)). */
+typedef struct sbmp_fold_info {
+    int window;         /* rows of the ring = the most iterations one fold takes (64) */
+    int keysPerGroup;   /* the most keys one fold workgroup takes (65,280) */
+    int maxR2;          /* the largest nR2 the 16-bit key log serves (32,767) */
+    int maxRanks;       /* the largest nranks (8) */
+    int groups, per;    /* for logSlots: ceil(logSlots / keysPerGroup), and ceil(logSlots / groups)
+                           rounded up to a multiple of 8 */
+} sbmp_fold_info;
+sbmp_status sbmp_fold_r2_info(int logSlots, sbmp_fold_info* out);
+sbmp_status sbmp_fold_r2_batch(const uint16_t* d_ring, const int* S, const int* executed, int tFirst, int tLast,
+                               int logSlots, int nR2, int rank, int nranks, int* d_R2Valid, int* d_R2Invalid,
+                               void* stream /* hipStream_t; NULL: default */);
+sbmp_status sbmp_fold_r2_batch_host(const uint16_t* ring, const int* S, const int* executed, int tFirst, int tLast,
+                                    int logSlots, int nR2, int rank, int nranks, int* R2Valid, int* R2Invalid);
+
 /* sbmp_tree_query_batch: the goal query of sbmp_kgmt_query_goals (k_tree_query) over caller
  * rows: d_state and d_ctrl are device arrays of rows x 4 floats, (x, y, -, -) and
  * (-, -, -, cost), the planner's tree layout; 1 <= rows < 2^31.  goals and out are host

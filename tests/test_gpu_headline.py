@@ -9,7 +9,8 @@ bit-exact against the CPU oracle -- not properties.
       complete GNew clear, seed 20240807, 72 iterations: covers the driver's timed
       window (iterations 6-25 of `bench.py --warmup 5 --steps 20`) and bench.py's own
       default window (21-70), including the steady state where the planner workgroup
-      inserts (A <= kPlannerInsertMax) and the R2 key-log folds at 32 and 64.
+      inserts (A <= kPlannerInsertMax) and the R2 key-log fold at 64 (the window is 64
+      iterations; the rest is folded at the export).
   c3r the same with the reference's partial GNew clear (D6), 40 iterations.
   c2  the R2 point agent at 262,144 samples/iteration.
   c4  1,048,576 samples/iteration: on one rank (more blocks than one launch holds)
