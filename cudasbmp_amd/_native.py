@@ -135,6 +135,20 @@ class FoldInfo(ctypes.Structure):   # sbmp_fold_info
     _fields_ = [(n, ctypes.c_int) for n in ("window", "keysPerGroup", "maxR2", "maxRanks", "groups", "per")]
 
 
+class TreeExtract(ctypes.Structure):   # sbmp_tree_extract
+    _fields_ = [(n, ctypes.c_int) for n in ("rows", "kept", "below", "masked", "detached", "root")] + [
+        ("rootCost", ctypes.c_float)]
+
+
+class TreeExtractArgs(ctypes.Structure):   # sbmp_tree_extract_args
+    _fields_ = [("state", ctypes.c_void_p), ("ctrl", ctypes.c_void_p), ("parent", ctypes.c_void_p),
+                ("rows", ctypes.c_int), ("depthBound", ctypes.c_int)]
+
+
+class TreeExtractLayout(ctypes.Structure):   # sbmp_tree_extract_layout
+    _fields_ = [(n, ctypes.c_int) for n in ("tileRows", "roundTiles", "tiles", "rounds")]
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", ctypes.c_longlong), ("totalMs", ctypes.c_double)]
 
@@ -164,6 +178,7 @@ EXPORTED_SYMBOLS = (
     "sbmp_tree_query_alive_batch", "sbmp_tree_query_alive_batch_host",
     "sbmp_kgmt_resample_paths", "sbmp_tree_resample_batch", "sbmp_tree_resample_batch_host",
     "sbmp_fold_r2_info", "sbmp_fold_r2_batch", "sbmp_fold_r2_batch_host",
+    "sbmp_kgmt_extract_tree", "sbmp_tree_extract_batch", "sbmp_tree_extract_batch_host", "sbmp_tree_extract_info",
 )
 
 _lib = None
@@ -271,6 +286,11 @@ def lib():
                                      P(ctypes.c_longlong), vp],
         "sbmp_tree_resample_batch_host": [P(TreePathsArgs), vp, i, ctypes.c_double, vp, vp, vp, vp, vp,
                                           ctypes.c_longlong, P(ctypes.c_longlong)],
+        "sbmp_kgmt_extract_tree": [vp, i, i, vp, vp, vp, vp, vp, ctypes.c_longlong, P(TreeExtract)],
+        "sbmp_tree_extract_batch": [P(TreeExtractArgs), i, vp, vp, vp, vp, vp, vp, ctypes.c_longlong, P(TreeExtract), vp],
+        "sbmp_tree_extract_batch_host": [P(TreeExtractArgs), i, vp, vp, vp, vp, vp, vp, ctypes.c_longlong,
+                                         P(TreeExtract)],
+        "sbmp_tree_extract_info": [ctypes.c_longlong, P(TreeExtractLayout)],
         "sbmp_fold_r2_info": [i, P(FoldInfo)],
         "sbmp_fold_r2_batch": [vp, vp, vp, i, i, i, i, i, i, vp, vp, vp],
         "sbmp_fold_r2_batch_host": [vp, vp, vp, i, i, i, i, i, i, vp, vp],

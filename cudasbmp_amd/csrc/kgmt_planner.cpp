@@ -1259,6 +1259,26 @@ void KgmtPlanner::resample_paths(const int* nodes, int count, double period, int
                          times, false, capacity, total, stream_);
 }
 
+// Prune and re-root (tree_extract.hip): as solution_paths, behind everything enqueued, reading the
+// tree (and, with useAlive, the last re-check's mask) only, into buffers of the call's own.
+void KgmtPlanner::extract_tree(int root, bool useAlive, float* state, float* ctrl, int* parent, int* origin,
+                               int* newRow, long long capacity, sbmp_tree_extract* out) {
+    if (!out) throw Error(SBMP_ERR_INVALID_ARGUMENT, "out must be non-NULL");
+    *out = sbmp_tree_extract{0, 0, 0, 0, 0, root, 0.0f};
+    // checked before the wait, as query_goals_alive does; before begin() settled_rows' error is the one
+    if (useAlive && begun_ && aliveRows_ < 0) throw Error(SBMP_ERR_STATE, "no recheck_tree since the last begin()");
+    sbmp_plan_result r;
+    const int rows = settled_rows(true, &r);
+    if (useAlive && rows != aliveRows_)
+        throw Error(SBMP_ERR_STATE, "the tree has " + std::to_string(rows) + " rows, the last recheck_tree covered " +
+                                        std::to_string(aliveRows_) + ": re-check again");
+    out->rows = rows;
+    tree_extract_check_root(root, rows);
+    // a row inserted by iteration t lies at most t edges below the root
+    tree_extract_device(d_, rows, r.iterations + 1, root, useAlive ? alive_ : nullptr, state, ctrl, parent, origin, newRow,
+                        false, capacity, out, stream_);
+}
+
 unsigned long long* KgmtPlanner::alloc_scratch_u64() {
     if (!scratch_) scratch_ = alloc<unsigned long long>(8);
     return scratch_;

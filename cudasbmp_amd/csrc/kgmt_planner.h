@@ -104,6 +104,11 @@ public:
     // Reads the tree only.
     virtual void resample_paths(const int* nodes, int count, double period, int* counts, uint8_t* status, float* states,
                                 int* edges, double* times, long long capacity, long long* total) = 0;
+    // The subtree below `root` over the kept rows as a tree of its own (k_extract_*;
+    // include/sbmp/tree_extract.h), as sbmp_kgmt_extract_tree takes it: host arrays, *out set before
+    // a capacity error.  useAlive: the last recheck_tree's mask.  Reads the tree only.
+    virtual void extract_tree(int root, bool useAlive, float* state, float* ctrl, int* parent, int* origin, int* newRow,
+                              long long capacity, sbmp_tree_extract* out) = 0;
     void export_csv(const std::string& dir);
 
     virtual std::vector<sbmp_kernel_stat> kernel_stats() = 0;
@@ -193,6 +198,21 @@ void tree_resample_batch(const sbmp_tree_paths_args* a, const int* nodes, int co
 void tree_resample_batch_host(const sbmp_tree_paths_args* a, const int* nodes, int count, double period, int* counts,
                               uint8_t* status, float* states, int* edges, double* times, long long capacity,
                               long long* total);
+
+// Prune and re-root (tree_extract.hip; include/sbmp/tree_extract.h).  d: the tree pointers; `rows`
+// rows, 0 <= root < rows (tree_extract_check_root).  d_keep: rows device bytes, or null (every row
+// is kept).  The outputs are host memory, or device memory with deviceOut set; each may be null.
+// *out is set before a capacity error.  Runs on `stream` and waits for the result; scratch is per call.
+void tree_extract_check_root(int root, int rows);
+void tree_extract_device(const KgmtDev& d, int rows, int depthBound, int root, const uint8_t* d_keep, float* state,
+                         float* ctrl, int* parent, int* origin, int* newRow, bool deviceOut, long long capacity,
+                         sbmp_tree_extract* out, hipStream_t stream);
+void tree_extract_batch(const sbmp_tree_extract_args* a, int root, const uint8_t* d_keep, float* d_state, float* d_ctrl,
+                        int* d_parent, int* d_origin, int* d_newRow, long long capacity, sbmp_tree_extract* out,
+                        hipStream_t stream);
+void tree_extract_batch_host(const sbmp_tree_extract_args* a, int root, const uint8_t* keep, float* state, float* ctrl,
+                             int* parent, int* origin, int* newRow, long long capacity, sbmp_tree_extract* out);
+void tree_extract_info(long long rows, sbmp_tree_extract_layout* out);
 
 // Times kernel launches of `ids` kinds with event pairs: the pairs are handed to
 // hipExtLaunchKernelGGL, which stamps them with the kernel's own start/end.
@@ -287,6 +307,8 @@ public:
     void trace_rows(const int* rows, long long count, float* steps, uint8_t* status) override;
     void resample_paths(const int* nodes, int count, double period, int* counts, uint8_t* status, float* states,
                         int* edges, double* times, long long capacity, long long* total) override;
+    void extract_tree(int root, bool useAlive, float* state, float* ctrl, int* parent, int* origin, int* newRow,
+                      long long capacity, sbmp_tree_extract* out) override;
 
     std::vector<sbmp_kernel_stat> kernel_stats() override;
     void path_info(sbmp_path_info* out) override;
@@ -454,6 +476,11 @@ public:
                         int* edges, double* times, long long capacity, long long* total) override {
         sync();
         r0().resample_paths(nodes, count, period, counts, status, states, edges, times, capacity, total);
+    }
+    void extract_tree(int root, bool useAlive, float* state, float* ctrl, int* parent, int* origin, int* newRow,
+                      long long capacity, sbmp_tree_extract* out) override {
+        sync();
+        r0().extract_tree(root, useAlive, state, ctrl, parent, origin, newRow, capacity, out);
     }
 
     std::vector<sbmp_kernel_stat> kernel_stats() override { return r0().kernel_stats(); }

@@ -296,6 +296,27 @@ sbmp_status sbmp_tree_resample_batch_host(const sbmp_tree_paths_args* args, cons
     });
 }
 
+sbmp_status sbmp_tree_extract_batch(const sbmp_tree_extract_args* args, int root, const uint8_t* d_keep, float* d_state,
+                                    float* d_ctrl, int* d_parent, int* d_origin, int* d_newRow, long long capacity,
+                                    sbmp_tree_extract* out, void* stream) {
+    return guarded([&] {
+        sbmp::tree_extract_batch(args, root, d_keep, d_state, d_ctrl, d_parent, d_origin, d_newRow, capacity, out,
+                                 static_cast<hipStream_t>(stream));
+    });
+}
+
+sbmp_status sbmp_tree_extract_batch_host(const sbmp_tree_extract_args* args, int root, const uint8_t* keep, float* state,
+                                         float* ctrl, int* parent, int* origin, int* newRow, long long capacity,
+                                         sbmp_tree_extract* out) {
+    return guarded([&] {
+        sbmp::tree_extract_batch_host(args, root, keep, state, ctrl, parent, origin, newRow, capacity, out);
+    });
+}
+
+sbmp_status sbmp_tree_extract_info(long long rows, sbmp_tree_extract_layout* out) {
+    return guarded([&] { sbmp::tree_extract_info(rows, out); });
+}
+
 sbmp_status sbmp_goal_radius_threshold(float r, float* t) {
     return guarded([&] {
         REQUIRE(t, "t must be non-NULL");
@@ -534,6 +555,14 @@ sbmp_status sbmp_kgmt_resample_paths(sbmp_kgmt* h, const int* nodes, int count, 
     return guarded([&] {
         PLANNER(h);
         P.resample_paths(nodes, count, period, counts, status, states, edges, times, capacity, total);
+    });
+}
+
+sbmp_status sbmp_kgmt_extract_tree(sbmp_kgmt* h, int root, int useAlive, float* state, float* ctrl, int* parent,
+                                   int* origin, int* newRow, long long capacity, sbmp_tree_extract* out) {
+    return guarded([&] {
+        PLANNER(h);
+        P.extract_tree(root, useAlive != 0, state, ctrl, parent, origin, newRow, capacity, out);
     });
 }
 

@@ -1,6 +1,6 @@
 // tree_pass.h — the host-side plumbing of a pass over a grown tree, stated once for
-// tree_query.hip, tree_recheck.hip, tree_paths.hip and tree_resample.hip (DESIGN.md §5.8–5.10,
-// §5.12).  What a new tree pass gets for free:
+// tree_query.hip, tree_recheck.hip, tree_paths.hip, tree_resample.hip and tree_extract.hip
+// (DESIGN.md §5.8–5.10, §5.12, §5.13).  What a new tree pass gets for free:
 //   resident_grid            the grid of a grid-stride kernel: what the device holds at once,
 //                            no more than the work needs, and the one error when nothing fits
 //   DevBufs                  the device buffers of one call, freed with it

@@ -331,6 +331,18 @@ class KGMT:
         return resample_dict(lambda *o: nat.call("sbmp_kgmt_resample_paths", self._h, n, len(nodes),
                                                  ctypes.c_double(float(period)), *o), nodes)
 
+    def extract(self, root: int = 0, alive: bool = False) -> dict:
+        """The subtree below row `root` as a tree of its own, in one device pass
+        (sbmp_kgmt_extract_tree; include/sbmp/tree_extract.h): the rows whose parent chain reaches
+        `root` through kept rows only, numbered densely in their old order with their parents
+        rewritten.  alive=True keeps the rows the last recheck() left alive; otherwise every row.
+        Returns state (kept, 4), ctrl (kept, 4) with the stored cost in column 3, parent (kept,)
+        with -1 for the new root, origin (kept,) (the row of tree() a new row came from), newRow
+        (rows,) (-1 for a row that is no member) and summary, a dict rows, kept, below, masked,
+        detached, root, rootCost.  The plan goes on unchanged."""
+        from .tree_extract import extract_dict
+        return extract_dict(lambda *o: nat.call("sbmp_kgmt_extract_tree", self._h, int(root), int(bool(alive)), *o), None)
+
     def query_goals(self, goals, radius=None, alive: bool = False) -> dict:
         """Goal discs against the tree as it stands (sbmp_kgmt_query_goals; one k_tree_query pass
         per 16 goals): goals is (Q, 2) with one radius for all, or (Q, 3) rows of (x, y, radius).

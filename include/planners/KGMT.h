@@ -163,7 +163,30 @@ public:
                             std::vector<double>& times) const {
         return resamplePathsOf(h_, nodes, period, counts, status, states, edges, times);
     }
+    // The subtree below `root` as a tree of its own, in one device pass (sbmp_kgmt_extract_tree;
+    // sbmp/tree_extract.h): the rows whose parent chain reaches `root` through kept rows only
+    // (useAlive: the rows the last recheckTree left alive; else every row), numbered densely in
+    // their old order.  state and ctrl hold 4 floats per new row, parent -1 for the new root,
+    // origin the old row of every new row, newRow the new row of every old one (-1: no member).
+    sbmp_tree_extract extractTree(int root, bool useAlive, std::vector<float>& state, std::vector<float>& ctrl,
+                                  std::vector<int>& parent, std::vector<int>& origin, std::vector<int>& newRow) const {
+        return extractTreeOf(h_, root, useAlive, state, ctrl, parent, origin, newRow);
+    }
     // The two calls on any planner handle (KGMTBatch passes a member's).
+    static sbmp_tree_extract extractTreeOf(sbmp_kgmt* h, int root, bool useAlive, std::vector<float>& state,
+                                           std::vector<float>& ctrl, std::vector<int>& parent, std::vector<int>& origin,
+                                           std::vector<int>& newRow) {
+        sbmp_tree_extract s{};
+        SBMP_CHECK(sbmp_kgmt_extract_tree(h, root, useAlive ? 1 : 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &s));
+        state.assign(4 * (size_t)s.kept, 0.0f);
+        ctrl.assign(4 * (size_t)s.kept, 0.0f);
+        parent.assign((size_t)s.kept, 0);
+        origin.assign((size_t)s.kept, 0);
+        newRow.assign((size_t)s.rows, -1);
+        SBMP_CHECK(sbmp_kgmt_extract_tree(h, root, useAlive ? 1 : 0, state.data(), ctrl.data(), parent.data(),
+                                          origin.data(), newRow.data(), s.kept, &s));
+        return s;
+    }
     static long long solutionPathsOf(sbmp_kgmt* h, const std::vector<int>& nodes, std::vector<int>& lengths,
                                      std::vector<uint8_t>& status, std::vector<int>& rows, std::vector<float>& samples,
                                      std::vector<float>* costs) {

@@ -112,6 +112,11 @@ public:
                             std::vector<double>& times) const {
         return KGMT::resamplePathsOf(member(i), nodes, period, counts, status, states, edges, times);
     }
+    // Member i's subtree below `root` as a tree of its own (KGMT::extractTree).
+    sbmp_tree_extract extractTree(int i, int root, bool useAlive, std::vector<float>& state, std::vector<float>& ctrl,
+                                  std::vector<int>& parent, std::vector<int>& origin, std::vector<int>& newRow) const {
+        return KGMT::extractTreeOf(member(i), root, useAlive, state, ctrl, parent, origin, newRow);
+    }
     sbmp_kgmt_batch* handle() const { return h_; }
 
 private:

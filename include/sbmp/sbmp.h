@@ -359,6 +359,33 @@ sbmp_status sbmp_kgmt_resample_paths(sbmp_kgmt* h, const int* nodes, int count, 
                                      uint8_t* status, float* states, int* edges, double* times, long long capacity,
                                      long long* total);
 
+/* The usable subtree as a tree of its own: prune and re-root (include/sbmp/tree_extract.h states
+ * the rule; no reference counterpart).  Over the rows [0, R), R = min(treeSize,
+ * maxTreeSize), a row is a member iff its parent chain reaches `root` through kept rows only;
+ * the members are numbered densely in their old order (the root becomes row 0), their parents
+ * rewritten, and their stored state and controls copied bit for bit, costs included: costs stay
+ * measured from the original root, and rootCost is the stored cost of `root`.  Every row has
+ * one class, the first match: below (r < root), masked (not kept), detached (kept, but its
+ * parent is no member), kept. */
+typedef struct sbmp_tree_extract {
+    int rows, kept, below, masked, detached;   /* rows = kept + below + masked + detached */
+    int root;
+    float rootCost;                            /* ctrl[root].w as stored */
+} sbmp_tree_extract;
+/* useAlive != 0: a row is kept iff the last sbmp_kgmt_recheck_tree left it alive (SBMP_ERR_STATE
+ * without a re-check since the last begin(), or when the tree has grown since, exactly as
+ * sbmp_kgmt_query_goals_alive); 0: every row is kept.  Host outputs, each may be NULL: state and
+ * ctrl (4 floats per member), parent and origin (the member's old row) hold `capacity` rows,
+ * newRow holds R ints (the new row of every old row, -1 for a row that is no member).  *out is
+ * set in every case: with capacity < out->kept and any of the four member-sized outputs given the
+ * call fails with SBMP_ERR_INVALID_ARGUMENT, so a NULL / 0 call returns the size to allocate.  A
+ * root that is not kept gives kept = 0: an answer, not an error.  root outside [0, R) or out
+ * NULL: SBMP_ERR_INVALID_ARGUMENT.  Before the first begin(): SBMP_ERR_STATE.  State, waiting
+ * and handles as sbmp_kgmt_solution_paths: it only reads the tree (k_extract_* on the planner's
+ * stream over buffers of the call's own), and the plan goes on unchanged. */
+sbmp_status sbmp_kgmt_extract_tree(sbmp_kgmt* h, int root, int useAlive, float* state, float* ctrl, int* parent,
+                                   int* origin, int* newRow, long long capacity, sbmp_tree_extract* out);
+
 sbmp_status sbmp_kgmt_kernel_stats(sbmp_kgmt* h, sbmp_kernel_stat* out, int capacity, int* count);
 /* The form of the hot path chosen at the last begin() (sbmp_path_info). */
 sbmp_status sbmp_kgmt_path_info(sbmp_kgmt* h, sbmp_path_info* out);
@@ -587,6 +614,40 @@ sbmp_status sbmp_tree_resample_batch(const sbmp_tree_paths_args* args, const int
 sbmp_status sbmp_tree_resample_batch_host(const sbmp_tree_paths_args* args, const int* nodes, int count, double period,
                                           int* counts, uint8_t* status, float* states, int* edges, double* times,
                                           long long capacity, long long* total);
+/* sbmp_tree_extract_batch: the extraction of sbmp_kgmt_extract_tree over caller rows in the
+ * planner's tree layout (state, ctrl, parent as sbmp_tree_recheck_args; 1 <= rows < 2^31).
+ * depthBound: an upper bound on the rows of any parent chain, which sets the number of
+ * pointer-jumping passes; <= 0: rows, always sufficient.  Everything is device memory, so the
+ * result can stay there: d_keep (rows bytes, a row is kept iff its byte is non-zero; NULL: every
+ * row is kept), d_state, d_ctrl, d_parent and d_origin (`capacity` rows each) and d_newRow (rows
+ * ints); each output may be NULL.  *out (host) and the capacity protocol as
+ * sbmp_kgmt_extract_tree.  Waits for the result.  The result takes every step-level entry above
+ * as it is.  sbmp_tree_extract_batch_host takes the same arrays in host memory and applies the
+ * literal rule in plain loops (extract_rows_host of include/sbmp/tree_extract.h): a second
+ * statement of the rule, and it needs no device. */
+typedef struct sbmp_tree_extract_args {
+    const float* state;
+    const float* ctrl;
+    const int* parent;
+    int rows;
+    int depthBound;
+} sbmp_tree_extract_args;
+sbmp_status sbmp_tree_extract_batch(const sbmp_tree_extract_args* args, int root, const uint8_t* d_keep,
+                                    float* d_state, float* d_ctrl, int* d_parent, int* d_origin, int* d_newRow,
+                                    long long capacity, sbmp_tree_extract* out,
+                                    void* stream /* hipStream_t; NULL: default */);
+sbmp_status sbmp_tree_extract_batch_host(const sbmp_tree_extract_args* args, int root, const uint8_t* keep,
+                                         float* state, float* ctrl, int* parent, int* origin, int* newRow,
+                                         long long capacity, sbmp_tree_extract* out);
+/* The launcher's seams (host-only, no device needed): a tile is the rows one workgroup numbers
+ * in one go, and the offsets workgroup sums roundTiles tile counts per round.  0 <= rows < 2^31. */
+typedef struct sbmp_tree_extract_layout {
+    int tileRows;     /* rows per tile (1,024) */
+    int roundTiles;   /* tiles the offsets workgroup takes per round (256) */
+    int tiles;        /* for rows: ceil(rows / tileRows) */
+    int rounds;       /* for rows: ceil(tiles / roundTiles) */
+} sbmp_tree_extract_layout;
+sbmp_status sbmp_tree_extract_info(long long rows, sbmp_tree_extract_layout* out);
 
 /* The threshold the kernel compares d2 with (host-only, no device needed): *t = the largest
  * float d2 with sqrtf(d2) < r, found by bisecting the float bit patterns with that rule;
@@ -667,7 +728,7 @@ sbmp_status sbmp_kgmt_batch_enqueue(sbmp_kgmt_batch* h, int iterations);
 sbmp_status sbmp_kgmt_batch_sync(sbmp_kgmt_batch* h);
 sbmp_status sbmp_kgmt_batch_result(sbmp_kgmt_batch* h, int member, sbmp_plan_result* result);
 /* Member i as a planner handle owned by the batch, for every read-only call above
- * (copy_tree, copy_regions, copy_rng, iter_log, solution_path, solution_paths, trace_rows, resample_paths, query_goals, recheck_tree,
+ * (copy_tree, copy_regions, copy_rng, iter_log, solution_path, solution_paths, trace_rows, resample_paths, extract_tree, query_goals, recheck_tree,
  * query_goals_alive, state_hash,
  * export_csv, path_info, kernel_stats, ...).  sbmp_kgmt_plan / begin / step / enqueue / destroy on it fail
  * with SBMP_ERR_STATE, sbmp_kgmt_set_iteration_dump with SBMP_ERR_UNSUPPORTED. */
