@@ -149,6 +149,23 @@ class TreeExtractLayout(ctypes.Structure):   # sbmp_tree_extract_layout
     _fields_ = [(n, ctypes.c_int) for n in ("tileRows", "roundTiles", "tiles", "rounds")]
 
 
+class TreeAdoptArgs(ctypes.Structure):   # sbmp_tree_adopt_args
+    _fields_ = [("state", ctypes.c_void_p), ("ctrl", ctypes.c_void_p), ("parent", ctypes.c_void_p),
+                ("rows", ctypes.c_int), ("frontierFrom", ctypes.c_int), ("depthBound", ctypes.c_int),
+                ("onDevice", ctypes.c_int)]
+
+
+class TreeAdopt(ctypes.Structure):   # sbmp_tree_adopt
+    _fields_ = [(n, ctypes.c_int) for n in ("rows", "nonFinite", "frontierNonFinite", "outOfGrid", "goalRow",
+                                            "treeSize", "gLo")]
+
+
+class TreeAdoptTablesArgs(ctypes.Structure):   # sbmp_tree_adopt_tables_args
+    _fields_ = [("state", ctypes.c_void_p), ("rows", ctypes.c_int), ("frontierFrom", ctypes.c_int),
+                ("width", ctypes.c_float), ("height", ctypes.c_float), ("N", ctypes.c_int), ("n", ctypes.c_int),
+                ("goal", ctypes.c_void_p)]
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", ctypes.c_longlong), ("totalMs", ctypes.c_double)]
 
@@ -179,6 +196,7 @@ EXPORTED_SYMBOLS = (
     "sbmp_kgmt_resample_paths", "sbmp_tree_resample_batch", "sbmp_tree_resample_batch_host",
     "sbmp_fold_r2_info", "sbmp_fold_r2_batch", "sbmp_fold_r2_batch_host",
     "sbmp_kgmt_extract_tree", "sbmp_tree_extract_batch", "sbmp_tree_extract_batch_host", "sbmp_tree_extract_info",
+    "sbmp_kgmt_adopt_tree", "sbmp_kgmt_replan", "sbmp_tree_adopt_tables", "sbmp_tree_adopt_tables_host",
 )
 
 _lib = None
@@ -291,6 +309,10 @@ def lib():
         "sbmp_tree_extract_batch_host": [P(TreeExtractArgs), i, vp, vp, vp, vp, vp, vp, ctypes.c_longlong,
                                          P(TreeExtract)],
         "sbmp_tree_extract_info": [ctypes.c_longlong, P(TreeExtractLayout)],
+        "sbmp_kgmt_adopt_tree": [vp, P(TreeAdoptArgs), vp, vp, i, ctypes.c_uint64, P(TreeAdopt)],
+        "sbmp_kgmt_replan": [vp, i, i, i, vp, vp, i, ctypes.c_uint64, P(TreeAdopt)],
+        "sbmp_tree_adopt_tables": [P(TreeAdoptTablesArgs), vp, vp, vp, vp, vp, vp, P(TreeAdopt), vp],
+        "sbmp_tree_adopt_tables_host": [P(TreeAdoptTablesArgs), vp, vp, vp, vp, vp, vp, P(TreeAdopt)],
         "sbmp_fold_r2_info": [i, P(FoldInfo)],
         "sbmp_fold_r2_batch": [vp, vp, vp, i, i, i, i, i, i, vp, vp, vp],
         "sbmp_fold_r2_batch_host": [vp, vp, vp, i, i, i, i, i, i, vp, vp],

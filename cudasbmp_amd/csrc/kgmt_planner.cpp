@@ -584,6 +584,32 @@ void KgmtPlanner::check_begin_args(const float* initial, const float* goal, cons
 
 void KgmtPlanner::begin(const float* initial, const float* goal, const float* d_obstacles, int nObs, uint64_t seed) {
     check_begin_args(initial, goal, d_obstacles, nObs);
+    reset_plan(goal, d_obstacles, nObs);
+    KgmtDev& d = d_;
+    hipStream_t s = stream_;
+
+    // Root (KGMT.cu:85-97).
+    const int r1 = getR1(initial[0], initial[1], d.R1Size, d.N);
+    const int r2 = getR2(initial[0], initial[1], r1, d.R1Size, d.N, d.R2Size, d.n);
+    launch_seed_root(d, make_float4(initial[0], initial[1], initial[2], initial[3]),
+                     make_float4(initial[4], initial[5], initial[6], 0.0f), r1, r2, s);
+    // curand_init(seed, slot, 0) for every slot (KGMT.cu:109-111, D1).
+    launch_init_slots(d, curand_seed_state(seed), jumps_, nbits_, expandBlocks_, s);
+    SBMP_HIP(hipGetLastError());
+    // tests: SBMP_INJECT_WAIT_ERROR=<kErr*> starts the plan as if a bounded in-kernel wait
+    // had already given up, so the host's error paths can be exercised without a hang
+    if (const char* inj = getenv("SBMP_INJECT_WAIT_ERROR")) {
+        const int code = atoi(inj);
+        SBMP_HIP(hipStreamSynchronize(s));   // after k_seed_root's reset
+        SBMP_HIP(hipMemcpy(&d.status->error, &code, sizeof(int), hipMemcpyHostToDevice));
+    }
+    adoptedDepth_ = 1;
+    start_plan(1);
+}
+
+// The part of begin() before the seeding, shared with adopt_tree(): the clears of §5.11 on the
+// stream, the obstacle list, the form and the goal.
+void KgmtPlanner::reset_plan(const float* goal, const float* d_obstacles, int nObs) {
     SBMP_HIP(hipSetDevice(p_.device));
     KgmtDev& d = d_;
     hipStream_t s = stream_;
@@ -644,36 +670,125 @@ void KgmtPlanner::begin(const float* initial, const float* goal, const float* d_
     choose_form(d_obstacles, nObs);
     d.goalX = goal[0];
     d.goalY = goal[1];
+}
 
-    // Root (KGMT.cu:85-97).
-    const int r1 = getR1(initial[0], initial[1], d.R1Size, d.N);
-    const int r2 = getR2(initial[0], initial[1], r1, d.R1Size, d.N, d.R2Size, d.n);
-    launch_seed_root(d, make_float4(initial[0], initial[1], initial[2], initial[3]),
-                     make_float4(initial[4], initial[5], initial[6], 0.0f), r1, r2, s);
-    // curand_init(seed, slot, 0) for every slot (KGMT.cu:109-111, D1).
-    launch_init_slots(d, curand_seed_state(seed), jumps_, nbits_, expandBlocks_, s);
-    SBMP_HIP(hipGetLastError());
-    // tests: SBMP_INJECT_WAIT_ERROR=<kErr*> starts the plan as if a bounded in-kernel wait
-    // had already given up, so the host's error paths can be exercised without a hang
-    if (const char* inj = getenv("SBMP_INJECT_WAIT_ERROR")) {
-        const int code = atoi(inj);
-        SBMP_HIP(hipStreamSynchronize(s));   // after k_seed_root's reset
-        SBMP_HIP(hipMemcpy(&d.status->error, &code, sizeof(int), hipMemcpyHostToDevice));
-    }
-
-    t_next_ = 1;
-    lastFolded_ = 0;
+// The part of begin() after the seeding, shared with adopt_tree().  tFirst: the first iteration
+// the loop runs, 1 after begin(), 2 after an adoption (which stands for iteration 1: it wrote
+// ctrl[1] itself, and iteration 1 logged no R2 key, so the fold's window starts behind it).
+void KgmtPlanner::start_plan(int tFirst) {
+    KgmtDev& d = d_;
+    hipStream_t s = stream_;
+    t_next_ = tFirst;
+    firstIter_ = tFirst;
+    lastFolded_ = tFirst - 1;
     aliveRows_ = -1;   // the last re-check's alive mask was of another tree
     begun_ = true;
     wallMs_ = 0.0;
     wallFixed_ = false;
     SBMP_HIP(hipStreamSynchronize(s));
-    poll_->word = 0;   // no k_step of this plan has run (the stream is idle)
+    // no k_step of this plan has run (the stream is idle); the launches "seen" are those before tFirst
+    poll_->word = (unsigned long long)(tFirst - 1) << 2;
     if (ex_) ex_->barrier(s);   // every rank set up before the first (time-bounded) exchange
     t0_ = now_ms();
-    flushed_ = !d.stepMode;   // k_step(1) plans iteration 1 itself; two launches: nothing is ever pending
-    if (!d.stepMode) launch_finish(d, 0, 0, s, timing(K_FINISH));   // prepares iteration 1
+    flushed_ = !d.stepMode;   // k_step(tFirst) plans iteration tFirst itself; two launches: nothing is ever pending
+    if (!d.stepMode) launch_finish(d, tFirst - 1, 0, s, timing(K_FINISH));   // prepares iteration tFirst
     SBMP_HIP(hipGetLastError());
+}
+
+// A tree adopted as iteration 1 (tree_adopt.hip; include/sbmp/tree_adopt.h).
+// Everything that can refuse runs first and reads the caller's rows only, so a refused adoption
+// leaves the previous plan as it was.  Then begin()'s clears, the rows, the tables of both
+// parities, ctrl[1] and status, the slots, and the loop starts at iteration 2.
+void KgmtPlanner::adopt_tree(const sbmp_tree_adopt_args* a, const float* goal, const float* d_obstacles, int nObs,
+                             uint64_t seed, sbmp_tree_adopt* out) {
+    if (d_.sharded)
+        throw Error(SBMP_ERR_STATE, "adopting a tree is supported on a single-rank planner only, not on a sharded rank");
+    // the adoption stands for iteration 1 and plans iteration 2: ctrl[2] must exist (numIterations + 2 blocks)
+    if (p_.numIterations < 1)
+        throw Error(SBMP_ERR_STATE, "adopting a tree needs a planner with numIterations >= 1: the adoption is iteration 1");
+    if (!a || !out) throw Error(SBMP_ERR_INVALID_ARGUMENT, "args and out must be non-NULL");
+    if (!a->state || !a->ctrl || !a->parent)
+        throw Error(SBMP_ERR_INVALID_ARGUMENT, "state, ctrl and parent must be non-NULL");
+    if (!goal) throw Error(SBMP_ERR_INVALID_ARGUMENT, "goal must be non-NULL");
+    if (nObs < 0 || (nObs > 0 && !d_obstacles)) throw Error(SBMP_ERR_INVALID_ARGUMENT, "bad obstacles");
+    if (a->rows < 1 || a->rows > d_.M)
+        throw Error(SBMP_ERR_INVALID_ARGUMENT,
+                    "rows " + std::to_string(a->rows) + " is outside [1, maxTreeSize " + std::to_string(d_.M) + "]");
+    if (a->frontierFrom < 0 || a->frontierFrom > a->rows)
+        throw Error(SBMP_ERR_INVALID_ARGUMENT, "frontierFrom " + std::to_string(a->frontierFrom) + " is outside [0, " +
+                                                   std::to_string(a->rows) + "]");
+    if (!std::isfinite(goal[0]) || !std::isfinite(goal[1]))
+        throw Error(SBMP_ERR_INVALID_ARGUMENT, "the goal's x and y must be finite");
+    SBMP_HIP(hipSetDevice(p_.device));
+    const int R = a->rows;
+    hipStream_t s = stream_;
+    DevBufs w;
+    drained_on_throw(s, [&] {
+        const float* dState = a->state;
+        const float* dCtrl = a->ctrl;
+        const int* dParent = a->parent;
+        if (!a->onDevice) {   // host rows: the call's own device copy
+            float* us = w.alloc<float>(4 * (size_t)R);
+            float* uc = w.alloc<float>(4 * (size_t)R);
+            int* up = w.alloc<int>((size_t)R);
+            SBMP_HIP(hipMemcpyAsync(us, a->state, sizeof(float) * 4 * (size_t)R, hipMemcpyHostToDevice, s));
+            SBMP_HIP(hipMemcpyAsync(uc, a->ctrl, sizeof(float) * 4 * (size_t)R, hipMemcpyHostToDevice, s));
+            SBMP_HIP(hipMemcpyAsync(up, a->parent, sizeof(int) * (size_t)R, hipMemcpyHostToDevice, s));
+            dState = us;
+            dCtrl = uc;
+            dParent = up;
+        }
+        void* scratch = w.alloc<char>(tree_adopt_scratch_bytes(R));
+        tree_adopt_scan(d_, dState, R, a->frontierFrom, goal, scratch, out, s);   // waits
+        if (out->frontierNonFinite > 0)   // D15 extended: a non-finite parent would only propagate NaN children
+            throw Error(SBMP_ERR_INVALID_ARGUMENT, std::to_string(out->frontierNonFinite) +
+                                                       " rows of the frontier have a non-finite x, y, theta or v");
+        reset_plan(goal, d_obstacles, nObs);
+        tree_adopt_seed(d_, dState, dCtrl, dParent, R, a->frontierFrom, scratch, s);
+        launch_init_slots(d_, curand_seed_state(seed), jumps_, nbits_, expandBlocks_, s);
+        SBMP_HIP(hipGetLastError());
+        adoptedDepth_ = a->depthBound > 0 ? std::min(a->depthBound, R) : R;
+        start_plan(2);   // waits for the stream: the call's buffers are no longer read
+    });
+}
+
+// The handle's own tree, pruned and re-rooted into device memory of the call's own, adopted.
+void KgmtPlanner::replan(int root, bool useAlive, int frontierFrom, const float* goal, const float* d_obstacles,
+                         int nObs, uint64_t seed, sbmp_tree_adopt* out) {
+    if (d_.sharded)
+        throw Error(SBMP_ERR_STATE, "replanning by adoption is supported on a single-rank planner only, not on a sharded rank");
+    if (p_.numIterations < 1)
+        throw Error(SBMP_ERR_STATE, "adopting a tree needs a planner with numIterations >= 1: the adoption is iteration 1");
+    if (!out) throw Error(SBMP_ERR_INVALID_ARGUMENT, "out must be non-NULL");
+    if (useAlive && begun_ && aliveRows_ < 0) throw Error(SBMP_ERR_STATE, "no recheck_tree since the last begin()");
+    sbmp_plan_result r;
+    const int rows = settled_rows(true, &r);
+    if (useAlive && rows != aliveRows_)
+        throw Error(SBMP_ERR_STATE, "the tree has " + std::to_string(rows) + " rows, the last recheck_tree covered " +
+                                        std::to_string(aliveRows_) + ": re-check again");
+    tree_extract_check_root(root, rows);
+    DevBufs w;
+    drained_on_throw(stream_, [&] {   // nothing reads the call's buffers when they go
+        float* xs = w.alloc<float>(4 * (size_t)rows);
+        float* xc = w.alloc<float>(4 * (size_t)rows);
+        int* xp = w.alloc<int>((size_t)rows);
+        sbmp_tree_extract ex;
+        const int bound = depth_bound(r.iterations);
+        tree_extract_device(d_, rows, bound, root, useAlive ? alive_ : nullptr, xs, xc, xp, nullptr, nullptr, true, rows,
+                            &ex, stream_);
+        if (ex.kept < 1)
+            throw Error(SBMP_ERR_INVALID_ARGUMENT,
+                        "row " + std::to_string(root) + " is not kept: there is nothing to adopt");
+        sbmp_tree_adopt_args a{};
+        a.state = xs;
+        a.ctrl = xc;
+        a.parent = xp;
+        a.rows = ex.kept;
+        a.frontierFrom = frontierFrom;
+        a.depthBound = bound;
+        a.onDevice = 1;
+        adopt_tree(&a, goal, d_obstacles, nObs, seed, out);
+    });
 }
 
 void KgmtPlanner::choose_form(const float* d_obstacles, int nObs) {
@@ -956,7 +1071,8 @@ int KgmtPlanner::last_executed(const std::vector<IterCtrl>& c) const {
 bool KgmtPlanner::active() {
     if (!begun_) return false;
     flush();   // k_step mode: the flush pass writes ctrl[t_next] and the goal of t_next - 1
-    // ctrl has numIterations + 2 entries, so t_next <= numIterations + 1 is in range
+    // ctrl has numIterations + 2 entries, so t_next <= numIterations + 1 is in range (an adoption, which starts
+    // at t_next = 2, is refused on a planner with numIterations < 1)
     SBMP_HIP(hipMemcpyAsync(&poll_->ctrl, d_.ctrl + t_next_, sizeof(IterCtrl), hipMemcpyDeviceToHost, stream_));
     SBMP_HIP(hipMemcpyAsync(&poll_->status, d_.status, sizeof(PlannerStatus), hipMemcpyDeviceToHost, stream_));
     sync();
@@ -1104,7 +1220,8 @@ void KgmtPlanner::result(sbmp_plan_result* r) {
         r->costToGoal = gc.w;
     }
     r->wallMs = wallMs_;
-    r->stalled = (itr > 0 && c[itr].nG == 0) ? 1 : 0;
+    // an adoption's iteration 1 has nG == 0 by construction: only an iteration the loop ran can stall
+    r->stalled = (itr >= firstIter_ && c[itr].nG == 0) ? 1 : 0;
 }
 
 std::vector<sbmp_iter_record> KgmtPlanner::iter_log() {
@@ -1204,8 +1321,8 @@ void KgmtPlanner::recheck_tree(const float* d_obstacles, int nObs, uint8_t* stat
         aliveCap_ = rows;
     }
     // a row inserted by iteration t lies at most t edges below the root
-    tree_recheck_device(d_, p_.agent, expandVariant_, rows, r.iterations + 1, d_obstacles, nObs, alive_, status, out,
-                        stream_);
+    tree_recheck_device(d_, p_.agent, expandVariant_, rows, depth_bound(r.iterations), d_obstacles, nObs, alive_, status,
+                        out, stream_);
     aliveRows_ = rows;
 }
 
@@ -1233,8 +1350,8 @@ void KgmtPlanner::solution_paths(const int* nodes, int count, int* lengths, uint
     if (count == 0) return;
     tree_paths_check(nodes, count, R, total);
     // one level per iteration, plus the root: solution_path's bound
-    tree_paths_device(d_, R, p_.numIterations + 2, nodes, count, lengths, status, rows, samples, costs, capacity, total,
-                      stream_);
+    tree_paths_device(d_, R, depth_bound(p_.numIterations + 1), nodes, count, lengths, status, rows, samples, costs,
+                      capacity, total, stream_);
 }
 
 void KgmtPlanner::trace_rows(const int* rows, long long count, float* steps, uint8_t* status) {
@@ -1255,8 +1372,8 @@ void KgmtPlanner::resample_paths(const int* nodes, int count, double period, int
     const int R = settled_rows(count > 0);
     tree_resample_check(nodes, count, R, period, total);
     if (count == 0) return;
-    tree_resample_device(d_, p_.agent, R, p_.numIterations + 2, nodes, count, period, counts, status, states, edges,
-                         times, false, capacity, total, stream_);
+    tree_resample_device(d_, p_.agent, R, depth_bound(p_.numIterations + 1), nodes, count, period, counts, status, states,
+                         edges, times, false, capacity, total, stream_);
 }
 
 // Prune and re-root (tree_extract.hip): as solution_paths, behind everything enqueued, reading the
@@ -1275,8 +1392,8 @@ void KgmtPlanner::extract_tree(int root, bool useAlive, float* state, float* ctr
     out->rows = rows;
     tree_extract_check_root(root, rows);
     // a row inserted by iteration t lies at most t edges below the root
-    tree_extract_device(d_, rows, r.iterations + 1, root, useAlive ? alive_ : nullptr, state, ctrl, parent, origin, newRow,
-                        false, capacity, out, stream_);
+    tree_extract_device(d_, rows, depth_bound(r.iterations), root, useAlive ? alive_ : nullptr, state, ctrl, parent, origin,
+                        newRow, false, capacity, out, stream_);
 }
 
 unsigned long long* KgmtPlanner::alloc_scratch_u64() {
@@ -1293,7 +1410,10 @@ int KgmtPlanner::solution_path(int node, int* rows, float* samples, float* costs
     }
     const int rowsInTree = std::min(r.treeSize, d_.M);
     if (node >= rowsInTree) throw Error(SBMP_ERR_INVALID_ARGUMENT, "node is not a tree row");
-    const int maxDepth = p_.numIterations + 2;   // one level per iteration, plus the root
+    // one level per iteration, plus the root; after an adoption plus the adopted chains, and a
+    // chain is never longer than the tree
+    const int maxDepth =
+        adoptedDepth_ > 1 ? std::min(depth_bound(p_.numIterations + 1), std::max(rowsInTree, 1)) : p_.numIterations + 2;
     int* dI = nullptr;
     float* dF = nullptr;
     SBMP_HIP(hipMalloc(&dI, sizeof(int) * (1 + (size_t)maxDepth)));

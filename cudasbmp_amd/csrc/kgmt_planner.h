@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <functional>
 #include <stdexcept>
 #include <string>
@@ -109,6 +110,16 @@ public:
     // a capacity error.  useAlive: the last recheck_tree's mask.  Reads the tree only.
     virtual void extract_tree(int root, bool useAlive, float* state, float* ctrl, int* parent, int* origin, int* newRow,
                               long long capacity, sbmp_tree_extract* out) = 0;
+    // A tree adopted as the plan's iteration 1, and the handle's own extracted tree adopted
+    // (tree_adopt.hip; include/sbmp/tree_adopt.h), as sbmp_kgmt_adopt_tree / sbmp_kgmt_replan take
+    // them.  A single rank only: every other handle refuses (its exchange buffers carry
+    // iteration 1's counts by another route).
+    virtual void adopt_tree(const sbmp_tree_adopt_args*, const float*, const float*, int, uint64_t, sbmp_tree_adopt*) {
+        throw Error(SBMP_ERR_STATE, "adopting a tree is supported on a single-rank planner only, not on a shard group");
+    }
+    virtual void replan(int, bool, int, const float*, const float*, int, uint64_t, sbmp_tree_adopt*) {
+        throw Error(SBMP_ERR_STATE, "replanning by adoption is supported on a single-rank planner only, not on a shard group");
+    }
     void export_csv(const std::string& dir);
 
     virtual std::vector<sbmp_kernel_stat> kernel_stats() = 0;
@@ -214,6 +225,22 @@ void tree_extract_batch_host(const sbmp_tree_extract_args* a, int root, const ui
                              int* parent, int* origin, int* newRow, long long capacity, sbmp_tree_extract* out);
 void tree_extract_info(long long rows, sbmp_tree_extract_layout* out);
 
+// Adoption (tree_adopt.hip; include/sbmp/tree_adopt.h).  d: the planner's grid, goal threshold and
+// buffers.  tree_adopt_scan: k_adopt_scan over `rows` device rows with the goal (x, y) given, the
+// cells into `scratch` (device, tree_adopt_scratch_bytes(rows)), the summary to the host; it waits
+// and writes nothing of the planner's.  tree_adopt_seed: k_adopt_seed and k_adopt_tables queued on
+// `stream` behind the plan's clears, without a wait.  The tables pair: the same kernels (or the
+// plain loops) over caller rows and any grid, host outputs.
+size_t tree_adopt_scratch_bytes(int rows);
+void tree_adopt_scan(const KgmtDev& d, const float* d_state, int rows, int frontierFrom, const float* goalXY,
+                     void* scratch, sbmp_tree_adopt* out, hipStream_t stream);
+void tree_adopt_seed(const KgmtDev& d, const float* d_state, const float* d_ctrl, const int* d_parent, int rows,
+                     int frontierFrom, const void* scratch, hipStream_t stream);
+void tree_adopt_tables_device(const sbmp_tree_adopt_tables_args* a, int* R1, int* R1Avail, int* R1Valid, int* R1Invalid,
+                              int* R1Cov, uint32_t* R2bits, sbmp_tree_adopt* out, hipStream_t stream);
+void tree_adopt_tables_host(const sbmp_tree_adopt_tables_args* a, int* R1, int* R1Avail, int* R1Valid, int* R1Invalid,
+                            int* R1Cov, uint32_t* R2bits, sbmp_tree_adopt* out);
+
 // Times kernel launches of `ids` kinds with event pairs: the pairs are handed to
 // hipExtLaunchKernelGGL, which stamps them with the kernel's own start/end.
 class LaunchTimer {
@@ -309,6 +336,10 @@ public:
                         int* edges, double* times, long long capacity, long long* total) override;
     void extract_tree(int root, bool useAlive, float* state, float* ctrl, int* parent, int* origin, int* newRow,
                       long long capacity, sbmp_tree_extract* out) override;
+    void adopt_tree(const sbmp_tree_adopt_args* a, const float* goal, const float* d_obstacles, int nObs, uint64_t seed,
+                    sbmp_tree_adopt* out) override;
+    void replan(int root, bool useAlive, int frontierFrom, const float* goal, const float* d_obstacles, int nObs,
+                uint64_t seed, sbmp_tree_adopt* out) override;
 
     std::vector<sbmp_kernel_stat> kernel_stats() override;
     void path_info(sbmp_path_info* out) override;
@@ -381,6 +412,15 @@ private:
     int residentGroups_ = 0, neededGroups_ = 0;   // k_step residency at the last begin()
     bool formLogged_ = false;
     void choose_form(const float* d_obstacles, int nObs);
+    // what begin() and adopt_tree() share: the clears, the obstacle list and the form before the
+    // seeding, and the host-side state after it (tFirst: the first iteration the loop runs)
+    void reset_plan(const float* goal, const float* d_obstacles, int nObs);
+    void start_plan(int tFirst);
+    int firstIter_ = 1;       // the first iteration the loop runs: 1 after begin(), 2 after an adoption
+    int adoptedDepth_ = 1;    // rows of the longest parent chain the plan started from (begin(): the root)
+    int depth_bound(int executed) const {
+        return (int)std::min<long long>((long long)adoptedDepth_ + executed, 0x7fffffff);
+    }
     void build_grid(const float* d_obstacles, int nObs);
     unsigned long long* xRecv_ = nullptr;
     size_t xWords_ = 0;

@@ -566,6 +566,37 @@ sbmp_status sbmp_kgmt_extract_tree(sbmp_kgmt* h, int root, int useAlive, float* 
     });
 }
 
+sbmp_status sbmp_kgmt_adopt_tree(sbmp_kgmt* h, const sbmp_tree_adopt_args* args, const float goal[7],
+                                 const float* d_obstacles, int obstaclesCount, uint64_t seed, sbmp_tree_adopt* out) {
+    return guarded([&] {
+        PLANNER(h);
+        if (h->borrowed) throw Error(SBMP_ERR_STATE, "adopting a tree is not supported on a batch member");
+        P.adopt_tree(args, goal, d_obstacles, obstaclesCount, seed, out);
+    });
+}
+
+sbmp_status sbmp_kgmt_replan(sbmp_kgmt* h, int root, int useAlive, int frontierFrom, const float goal[7],
+                             const float* d_obstacles, int obstaclesCount, uint64_t seed, sbmp_tree_adopt* out) {
+    return guarded([&] {
+        PLANNER(h);
+        if (h->borrowed) throw Error(SBMP_ERR_STATE, "replanning by adoption is not supported on a batch member");
+        P.replan(root, useAlive != 0, frontierFrom, goal, d_obstacles, obstaclesCount, seed, out);
+    });
+}
+
+sbmp_status sbmp_tree_adopt_tables(const sbmp_tree_adopt_tables_args* args, int* R1, int* R1Avail, int* R1Valid,
+                                   int* R1Invalid, int* R1Cov, uint32_t* R2bits, sbmp_tree_adopt* out, void* stream) {
+    return guarded([&] {
+        sbmp::tree_adopt_tables_device(args, R1, R1Avail, R1Valid, R1Invalid, R1Cov, R2bits, out,
+                                       static_cast<hipStream_t>(stream));
+    });
+}
+
+sbmp_status sbmp_tree_adopt_tables_host(const sbmp_tree_adopt_tables_args* args, int* R1, int* R1Avail, int* R1Valid,
+                                        int* R1Invalid, int* R1Cov, uint32_t* R2bits, sbmp_tree_adopt* out) {
+    return guarded([&] { sbmp::tree_adopt_tables_host(args, R1, R1Avail, R1Valid, R1Invalid, R1Cov, R2bits, out); });
+}
+
 sbmp_status sbmp_kgmt_kernel_stats(sbmp_kgmt* h, sbmp_kernel_stat* out, int capacity, int* count) {
     return guarded([&] {
         PLANNER(h);

@@ -343,6 +343,26 @@ class KGMT:
         from .tree_extract import extract_dict
         return extract_dict(lambda *o: nat.call("sbmp_kgmt_extract_tree", self._h, int(root), int(bool(alive)), *o), None)
 
+    def adopt(self, samples, parents, costs, goal, d_obstacles, count: int, seed: int, frontier_from: int = 0,
+              depth_bound: int = 0) -> dict:
+        """Adopt a tree in place of begin() and iteration 1 (sbmp_kgmt_adopt_tree;
+        include/sbmp/tree_adopt.h): samples (R, 7), parents (R,), costs (R,) as tree() returns them,
+        or state (R, 4), parents, ctrl (R, 4) as extract() does.  Every row is seeded as the root is;
+        the loop goes on over the frontier, the rows [frontier_from, R).  depth_bound: the rows of
+        the longest parent chain (0: R).  Returns the summary, a dict rows, nonFinite,
+        frontierNonFinite, outOfGrid, goalRow, treeSize, gLo; step(), result(), tree(), regions(),
+        iter_log() and every tree pass then work as after begin(), row 1 of iter_log() being the
+        adoption."""
+        from .tree_adopt import adopt
+        return adopt(self, samples, parents, costs, goal, d_obstacles, count, seed, frontier_from, depth_bound)
+
+    def replan(self, goal, d_obstacles, count: int, seed: int, root: int = 0, alive: bool = False,
+               frontier_from: int = 0) -> dict:
+        """extract(root, alive) of the planner's own tree, on the device, adopted against another
+        goal and obstacle list (sbmp_kgmt_replan); frontier_from counts in the extracted numbering."""
+        from .tree_adopt import replan
+        return replan(self, goal, d_obstacles, count, seed, root, alive, frontier_from)
+
     def query_goals(self, goals, radius=None, alive: bool = False) -> dict:
         """Goal discs against the tree as it stands (sbmp_kgmt_query_goals; one k_tree_query pass
         per 16 goals): goals is (Q, 2) with one radius for all, or (Q, 3) rows of (x, y, radius).

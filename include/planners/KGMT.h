@@ -172,6 +172,33 @@ public:
                                   std::vector<int>& parent, std::vector<int>& origin, std::vector<int>& newRow) const {
         return extractTreeOf(h_, root, useAlive, state, ctrl, parent, origin, newRow);
     }
+    // A tree adopted in place of begin() and iteration 1 (sbmp_kgmt_adopt_tree; sbmp/tree_adopt.h):
+    // state and ctrl hold 4 floats per row (the cost in ctrl's .w), parent one int, as extractTree
+    // returns them.  The frontier is the row range [frontierFrom, rows); depthBound <= 0: rows.
+    // The loop goes on with sbmp_kgmt_step on handle().
+    sbmp_tree_adopt adoptTree(const std::vector<float>& state, const std::vector<float>& ctrl,
+                              const std::vector<int>& parent, const float* goal, const float* d_obstacles,
+                              int obstaclesCount, uint64_t seed, int frontierFrom = 0, int depthBound = 0) {
+        sbmp_tree_adopt_args a{};
+        a.state = state.data();
+        a.ctrl = ctrl.data();
+        a.parent = parent.data();
+        a.rows = (int)parent.size();
+        a.frontierFrom = frontierFrom;
+        a.depthBound = depthBound;
+        a.onDevice = 0;
+        sbmp_tree_adopt s{};
+        SBMP_CHECK(sbmp_kgmt_adopt_tree(h_, &a, goal, d_obstacles, obstaclesCount, seed, &s));
+        return s;
+    }
+    // The planner's own tree below `root` (useAlive: the rows the last recheckTree left alive)
+    // adopted against another goal and obstacle list (sbmp_kgmt_replan).
+    sbmp_tree_adopt replan(const float* goal, const float* d_obstacles, int obstaclesCount, uint64_t seed, int root = 0,
+                           bool useAlive = false, int frontierFrom = 0) {
+        sbmp_tree_adopt s{};
+        SBMP_CHECK(sbmp_kgmt_replan(h_, root, useAlive ? 1 : 0, frontierFrom, goal, d_obstacles, obstaclesCount, seed, &s));
+        return s;
+    }
     // The two calls on any planner handle (KGMTBatch passes a member's).
     static sbmp_tree_extract extractTreeOf(sbmp_kgmt* h, int root, bool useAlive, std::vector<float>& state,
                                            std::vector<float>& ctrl, std::vector<int>& parent, std::vector<int>& origin,

@@ -386,6 +386,50 @@ typedef struct sbmp_tree_extract {
 sbmp_status sbmp_kgmt_extract_tree(sbmp_kgmt* h, int root, int useAlive, float* state, float* ctrl, int* parent,
                                    int* origin, int* newRow, long long capacity, sbmp_tree_extract* out);
 
+/* Adopt a tree into a planner and plan on (include/sbmp/tree_adopt.h states the rule; DESIGN.md
+ * §5.14; no reference counterpart).  The adoption takes the place of begin() and of iteration 1:
+ * every one of the `rows` rows is seeded as the reference seeds its root (its R1 cell counted
+ * in R1 and R1Valid and made available, its R2 bit set, R1Cov the set bits of each R1 cell; a
+ * cell of -1 is not counted), the slots are re-seeded from `seed`, and the loop goes on with
+ * iteration 2 over the frontier, the row range [frontierFrom, rows): 0 expands every adopted
+ * row, `rows` none (the loop then runs without effect, D7).  The lowest adopted row inside the
+ * goal radius ends the plan before anything is expanded; rows == maxTreeSize runs no iteration:
+ * both are answers, not errors.  depthBound: an upper bound on the rows of any parent chain of
+ * the adopted tree (<= 0: rows); the tree passes add the executed iterations to it.  Row 1 of
+ * sbmp_kgmt_iter_log is the adoption (S = A = 0).  After the call every entry works as after
+ * sbmp_kgmt_begin.  R1Invalid and the R2 counters start at 0 and costs are taken as stored.
+ * rows < 1 or > maxTreeSize, frontierFrom outside [0, rows], a non-finite x, y, theta or v in a
+ * row of the frontier, a non-finite goal, a NULL array: SBMP_ERR_INVALID_ARGUMENT, with the
+ * handle's previous plan left as it was (rows below the frontier are adopted as stored: nothing
+ * integrates from them).  A sharded handle, a local shard group, a batch member, and a planner
+ * created with numIterations < 1 (the adoption is iteration 1 and plans iteration 2): SBMP_ERR_STATE.
+ * sbmp_plan_result.iterations counts the adoption; stalled looks at the iterations the loop ran. */
+typedef struct sbmp_tree_adopt_args {
+    const float* state;    /* rows x 4: x, y, theta, v */
+    const float* ctrl;     /* rows x 4: the edge's controls, the cost in .w */
+    const int* parent;     /* rows */
+    int rows;
+    int frontierFrom;
+    int depthBound;
+    int onDevice;          /* nonzero: the three arrays are device memory (an sbmp_tree_extract_batch result) */
+} sbmp_tree_adopt_args;
+typedef struct sbmp_tree_adopt {
+    int rows;
+    int nonFinite;           /* rows with a non-finite x, y, theta or v */
+    int frontierNonFinite;   /* ... of them in [frontierFrom, rows) */
+    int outOfGrid;           /* rows with an R1 or R2 cell of -1 */
+    int goalRow;             /* the lowest row inside the goal radius, -1 if none */
+    int treeSize, gLo;       /* what iteration 2 starts from: rows, frontierFrom */
+} sbmp_tree_adopt;
+sbmp_status sbmp_kgmt_adopt_tree(sbmp_kgmt* h, const sbmp_tree_adopt_args* args, const float goal[7],
+                                 const float* d_obstacles, int obstaclesCount, uint64_t seed, sbmp_tree_adopt* out);
+/* sbmp_kgmt_extract_tree of the handle's own tree (root, useAlive as there) into device memory of
+ * the call's own, then sbmp_kgmt_adopt_tree of the result: the copy is needed because the
+ * adoption clears the tree arrays.  frontierFrom counts in the extracted numbering.  A root that
+ * is not kept (nothing to adopt): SBMP_ERR_INVALID_ARGUMENT, the plan left as it was. */
+sbmp_status sbmp_kgmt_replan(sbmp_kgmt* h, int root, int useAlive, int frontierFrom, const float goal[7],
+                             const float* d_obstacles, int obstaclesCount, uint64_t seed, sbmp_tree_adopt* out);
+
 sbmp_status sbmp_kgmt_kernel_stats(sbmp_kgmt* h, sbmp_kernel_stat* out, int capacity, int* count);
 /* The form of the hot path chosen at the last begin() (sbmp_path_info). */
 sbmp_status sbmp_kgmt_path_info(sbmp_kgmt* h, sbmp_path_info* out);
@@ -648,6 +692,27 @@ typedef struct sbmp_tree_extract_layout {
     int rounds;       /* for rows: ceil(tiles / roundTiles) */
 } sbmp_tree_extract_layout;
 sbmp_status sbmp_tree_extract_info(long long rows, sbmp_tree_extract_layout* out);
+/* sbmp_tree_adopt_tables: the tables an adoption (sbmp_kgmt_adopt_tree) leaves, over caller rows
+ * and any grid: k_adopt_scan, k_adopt_seed and k_adopt_tables as the planner launches them.
+ * state: device memory, rows x 4.  1 <= rows < 2^31, 0 <= frontierFrom <= rows, width > 0,
+ * 1 <= N * N <= 256, 1 <= n <= 16; goal: host, (x, y, radius), or NULL for no disc.  Host outputs,
+ * each may be NULL: the five R1 tables of N * N ints, R2bits of ceil(N * N * n * n / 32) words
+ * (bit r2 & 31 of word r2 >> 5).  A non-finite frontier row is counted in *out, not refused.
+ * Waits for the result.  sbmp_tree_adopt_tables_host takes state in host memory and applies the
+ * literal rule in plain loops (adopt_tables_host of include/sbmp/tree_adopt.h). */
+typedef struct sbmp_tree_adopt_tables_args {
+    const float* state;
+    int rows;
+    int frontierFrom;
+    float width, height;   /* the cells derive from the width (KGMT.cu:13-14) */
+    int N, n;
+    const float* goal;
+} sbmp_tree_adopt_tables_args;
+sbmp_status sbmp_tree_adopt_tables(const sbmp_tree_adopt_tables_args* args, int* R1, int* R1Avail, int* R1Valid,
+                                   int* R1Invalid, int* R1Cov, uint32_t* R2bits, sbmp_tree_adopt* out,
+                                   void* stream /* hipStream_t; NULL: default */);
+sbmp_status sbmp_tree_adopt_tables_host(const sbmp_tree_adopt_tables_args* args, int* R1, int* R1Avail, int* R1Valid,
+                                        int* R1Invalid, int* R1Cov, uint32_t* R2bits, sbmp_tree_adopt* out);
 
 /* The threshold the kernel compares d2 with (host-only, no device needed): *t = the largest
  * float d2 with sqrtf(d2) < r, found by bisecting the float bit patterns with that rule;
