@@ -14,8 +14,9 @@ from .tree_paths import tree_paths_batch, tree_trace_batch  # noqa: F401
 from .tree_resample import tree_resample_batch  # noqa: F401
 from .tree_extract import tree_extract_batch, tree_extract_info  # noqa: F401
 from .tree_adopt import tree_adopt_tables  # noqa: F401
+from .tree_reanchor import tree_reanchor_batch  # noqa: F401
 from .fold import fold_r2_batch, fold_r2_info  # noqa: F401
 from .config import load_system_config, DEMO_INITIAL, DEMO_GOAL  # noqa: F401
 
-__all__ = ["KGMT", "KGMTBatch", "batch_pack", "goal_radius_threshold", "tree_query_batch", "tree_recheck_batch", "tree_paths_batch", "tree_trace_batch", "tree_resample_batch", "tree_extract_batch", "tree_extract_info", "tree_adopt_tables", "fold_r2_batch", "fold_r2_info", "DeviceBuffer", "read_obstacles_csv", "device_count", "reference_seed_from_time", "random_tree",
+__all__ = ["KGMT", "KGMTBatch", "batch_pack", "goal_radius_threshold", "tree_query_batch", "tree_recheck_batch", "tree_paths_batch", "tree_trace_batch", "tree_resample_batch", "tree_extract_batch", "tree_extract_info", "tree_adopt_tables", "tree_reanchor_batch", "fold_r2_batch", "fold_r2_info", "DeviceBuffer", "read_obstacles_csv", "device_count", "reference_seed_from_time", "random_tree",
            "load_system_config", "DEMO_INITIAL", "DEMO_GOAL", "NativeLibraryError", "SbmpError", "LIB_PATH"]

@@ -160,6 +160,10 @@ class TreeAdopt(ctypes.Structure):   # sbmp_tree_adopt
                                             "treeSize", "gLo")]
 
 
+class TreeReanchor(ctypes.Structure):   # sbmp_tree_reanchor
+    _fields_ = [(n, ctypes.c_int) for n in ("rows", "alive", "blocked", "orphan", "cut", "firstDead", "levels")]
+
+
 class TreeAdoptTablesArgs(ctypes.Structure):   # sbmp_tree_adopt_tables_args
     _fields_ = [("state", ctypes.c_void_p), ("rows", ctypes.c_int), ("frontierFrom", ctypes.c_int),
                 ("width", ctypes.c_float), ("height", ctypes.c_float), ("N", ctypes.c_int), ("n", ctypes.c_int),
@@ -197,6 +201,7 @@ EXPORTED_SYMBOLS = (
     "sbmp_fold_r2_info", "sbmp_fold_r2_batch", "sbmp_fold_r2_batch_host",
     "sbmp_kgmt_extract_tree", "sbmp_tree_extract_batch", "sbmp_tree_extract_batch_host", "sbmp_tree_extract_info",
     "sbmp_kgmt_adopt_tree", "sbmp_kgmt_replan", "sbmp_tree_adopt_tables", "sbmp_tree_adopt_tables_host",
+    "sbmp_kgmt_reanchor_tree", "sbmp_kgmt_replan_from", "sbmp_tree_reanchor_batch", "sbmp_tree_reanchor_batch_host",
 )
 
 _lib = None
@@ -313,6 +318,10 @@ def lib():
         "sbmp_kgmt_replan": [vp, i, i, i, vp, vp, i, ctypes.c_uint64, P(TreeAdopt)],
         "sbmp_tree_adopt_tables": [P(TreeAdoptTablesArgs), vp, vp, vp, vp, vp, vp, P(TreeAdopt), vp],
         "sbmp_tree_adopt_tables_host": [P(TreeAdoptTablesArgs), vp, vp, vp, vp, vp, vp, P(TreeAdopt)],
+        "sbmp_kgmt_reanchor_tree": [vp, i, vp, vp, i, vp, vp, vp, vp, vp, ctypes.c_longlong, P(TreeReanchor)],
+        "sbmp_kgmt_replan_from": [vp, i, vp, i, vp, vp, i, ctypes.c_uint64, P(TreeReanchor), P(TreeAdopt)],
+        "sbmp_tree_reanchor_batch": [P(TreeRecheckArgs), vp, vp, vp, vp, P(TreeReanchor), vp],
+        "sbmp_tree_reanchor_batch_host": [P(TreeRecheckArgs), vp, vp, vp, vp, P(TreeReanchor)],
         "sbmp_fold_r2_info": [i, P(FoldInfo)],
         "sbmp_fold_r2_batch": [vp, vp, vp, i, i, i, i, i, i, vp, vp, vp],
         "sbmp_fold_r2_batch_host": [vp, vp, vp, i, i, i, i, i, i, vp, vp],

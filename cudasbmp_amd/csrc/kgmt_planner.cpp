@@ -791,6 +791,97 @@ void KgmtPlanner::replan(int root, bool useAlive, int frontierFrom, const float*
     });
 }
 
+namespace {
+// d with another tree behind its pointers: the rows of an extraction or of a re-anchoring.
+KgmtDev with_tree(KgmtDev d, float* state, float* ctrl, int* parent) {
+    d.treeState = reinterpret_cast<float4*>(state);
+    d.treeCtrl = reinterpret_cast<float4*>(ctrl);
+    d.treeParent = parent;
+    return d;
+}
+}  // namespace
+
+// The subtree below `root`, every row kept, re-anchored on a measured state (tree_reanchor.hip;
+// include/sbmp/tree_reanchor.h): as extract_tree, behind everything enqueued,
+// reading the tree only, into buffers of the call's own.
+void KgmtPlanner::reanchor_tree(int root, const float* newRoot, const float* d_obstacles, int nObs, float* state,
+                                float* ctrl, int* parent, int* origin, uint8_t* status, long long capacity,
+                                sbmp_tree_reanchor* out) {
+    if (!out) throw Error(SBMP_ERR_INVALID_ARGUMENT, "out must be non-NULL");
+    *out = sbmp_tree_reanchor{0, 0, 0, 0, 0, -1, 0};
+    sbmp_plan_result r;
+    const int rows = settled_rows(true, &r);
+    tree_extract_check_root(root, rows);
+    DevBufs w;
+    drained_on_throw(stream_, [&] {
+        float* xs = w.alloc<float>(4 * (size_t)rows);
+        float* xc = w.alloc<float>(4 * (size_t)rows);
+        int* xp = w.alloc<int>((size_t)rows);
+        int* xo = w.alloc<int>((size_t)rows);
+        sbmp_tree_extract ex;
+        const int bound = depth_bound(r.iterations);   // of the whole tree: no chain below `root` is longer
+        tree_extract_device(d_, rows, bound, root, nullptr, xs, xc, xp, xo, nullptr, true, rows, &ex, stream_);
+        const int kept = ex.kept;   // >= 1: every row is kept, the root among them
+        out->rows = kept;
+        if ((state || ctrl || parent || origin || status) && capacity < kept)
+            throw Error(SBMP_ERR_INVALID_ARGUMENT,
+                        "capacity " + std::to_string(capacity) + " < rows " + std::to_string(kept));
+        float* ns = w.alloc<float>(4 * (size_t)kept);
+        tree_reanchor_device(with_tree(d_, xs, xc, xp), p_.agent, expandVariant_, kept, bound, newRoot, d_obstacles, nObs,
+                             ns, nullptr, status, out, stream_);
+        read_back(stream_, {{state, ns, sizeof(float) * 4 * (size_t)kept},
+                            {ctrl, xc, sizeof(float) * 4 * (size_t)kept},
+                            {parent, xp, sizeof(int) * (size_t)kept},
+                            {origin, xo, sizeof(int) * (size_t)kept}});
+    });
+}
+
+// The handle's own tree re-rooted at `root`, re-anchored on the measured state, pruned to the
+// rows that stay alive and adopted, all in device memory of the call's own.  Everything before
+// adopt_tree only reads the plan, and adopt_tree refuses before it touches it.
+void KgmtPlanner::replan_from(int root, const float* newRoot, int frontierFrom, const float* goal,
+                              const float* d_obstacles, int nObs, uint64_t seed, sbmp_tree_reanchor* reanchorOut,
+                              sbmp_tree_adopt* out) {
+    if (d_.sharded)
+        throw Error(SBMP_ERR_STATE, "replanning by adoption is supported on a single-rank planner only, not on a sharded rank");
+    if (p_.numIterations < 1)
+        throw Error(SBMP_ERR_STATE, "adopting a tree needs a planner with numIterations >= 1: the adoption is iteration 1");
+    if (!out) throw Error(SBMP_ERR_INVALID_ARGUMENT, "out must be non-NULL");
+    sbmp_plan_result r;
+    const int rows = settled_rows(true, &r);
+    tree_extract_check_root(root, rows);
+    DevBufs w;
+    drained_on_throw(stream_, [&] {   // nothing reads the call's buffers when they go
+        float* xs = w.alloc<float>(4 * (size_t)rows);
+        float* xc = w.alloc<float>(4 * (size_t)rows);
+        int* xp = w.alloc<int>((size_t)rows);
+        sbmp_tree_extract ex;
+        const int bound = depth_bound(r.iterations);
+        tree_extract_device(d_, rows, bound, root, nullptr, xs, xc, xp, nullptr, nullptr, true, rows, &ex, stream_);
+        const int kept = ex.kept;   // >= 1: every row is kept, the root among them
+        float* ns = w.alloc<float>(4 * (size_t)kept);
+        uint8_t* alive = w.alloc<uint8_t>((size_t)kept);
+        sbmp_tree_reanchor ra;
+        tree_reanchor_device(with_tree(d_, xs, xc, xp), p_.agent, expandVariant_, kept, bound, newRoot, d_obstacles, nObs,
+                             ns, alive, nullptr, &ra, stream_);
+        if (reanchorOut) *reanchorOut = ra;
+        float* ys = w.alloc<float>(4 * (size_t)ra.alive);
+        float* yc = w.alloc<float>(4 * (size_t)ra.alive);
+        int* yp = w.alloc<int>((size_t)ra.alive);
+        tree_extract_device(with_tree(d_, ns, xc, xp), kept, bound, 0, alive, ys, yc, yp, nullptr, nullptr, true, ra.alive,
+                            &ex, stream_);   // row 0 is alive: ex.kept == ra.alive >= 1
+        sbmp_tree_adopt_args a{};
+        a.state = ys;
+        a.ctrl = yc;
+        a.parent = yp;
+        a.rows = ex.kept;
+        a.frontierFrom = frontierFrom;
+        a.depthBound = bound;
+        a.onDevice = 1;
+        adopt_tree(&a, goal, d_obstacles, nObs, seed, out);
+    });
+}
+
 void KgmtPlanner::choose_form(const float* d_obstacles, int nObs) {
     KgmtDev& d = d_;
     // k_step's expanders wait for workgroup 0, so every workgroup of the launch must be

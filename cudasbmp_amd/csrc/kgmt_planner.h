@@ -120,6 +120,17 @@ public:
     virtual void replan(int, bool, int, const float*, const float*, int, uint64_t, sbmp_tree_adopt*) {
         throw Error(SBMP_ERR_STATE, "replanning by adoption is supported on a single-rank planner only, not on a shard group");
     }
+    // The subtree below `root` (every row kept) re-anchored on a measured state (k_reanchor_*;
+    // include/sbmp/tree_reanchor.h), as sbmp_kgmt_reanchor_tree takes it: host arrays in the
+    // extracted numbering, *out set before a capacity error.  Reads the tree only.
+    virtual void reanchor_tree(int root, const float* newRoot, const float* d_obstacles, int nObs, float* state,
+                               float* ctrl, int* parent, int* origin, uint8_t* status, long long capacity,
+                               sbmp_tree_reanchor* out) = 0;
+    // extract, re-anchor, extract the alive rows, adopt: sbmp_kgmt_replan_from.  A single rank only.
+    virtual void replan_from(int, const float*, int, const float*, const float*, int, uint64_t, sbmp_tree_reanchor*,
+                             sbmp_tree_adopt*) {
+        throw Error(SBMP_ERR_STATE, "replanning by adoption is supported on a single-rank planner only, not on a shard group");
+    }
     void export_csv(const std::string& dir);
 
     virtual std::vector<sbmp_kernel_stat> kernel_stats() = 0;
@@ -241,6 +252,19 @@ void tree_adopt_tables_device(const sbmp_tree_adopt_tables_args* a, int* R1, int
 void tree_adopt_tables_host(const sbmp_tree_adopt_tables_args* a, int* R1, int* R1Avail, int* R1Valid, int* R1Invalid,
                             int* R1Cov, uint32_t* R2bits, sbmp_tree_adopt* out);
 
+// Re-anchoring (tree_reanchor.hip; include/sbmp/tree_reanchor.h).  base: the plan's parameters
+// and the tree pointers (root = row 0); newRoot: host, 4 finite floats; the list and the form as
+// for tree_recheck_device.  d_outState (rows x 4) and d_alive (rows bytes): device, or null;
+// status: host, or null.  A depthBound below the longest chain is refused (SBMP_ERR_INVALID_ARGUMENT)
+// before any row is replayed.  Waits for the result.
+void tree_reanchor_device(const KgmtDev& base, int agent, int variant, int rows, int depthBound, const float* newRoot,
+                          const float* d_obstacles, int nObs, float* d_outState, uint8_t* d_alive, uint8_t* status,
+                          sbmp_tree_reanchor* out, hipStream_t stream);
+void tree_reanchor_batch(const sbmp_tree_recheck_args* a, const float* newRoot, float* d_outState, uint8_t* d_alive,
+                         uint8_t* status, sbmp_tree_reanchor* out, hipStream_t stream);
+void tree_reanchor_batch_host(const sbmp_tree_recheck_args* a, const float* newRoot, float* outState, uint8_t* alive,
+                              uint8_t* status, sbmp_tree_reanchor* out);
+
 // Times kernel launches of `ids` kinds with event pairs: the pairs are handed to
 // hipExtLaunchKernelGGL, which stamps them with the kernel's own start/end.
 class LaunchTimer {
@@ -340,6 +364,10 @@ public:
                     sbmp_tree_adopt* out) override;
     void replan(int root, bool useAlive, int frontierFrom, const float* goal, const float* d_obstacles, int nObs,
                 uint64_t seed, sbmp_tree_adopt* out) override;
+    void reanchor_tree(int root, const float* newRoot, const float* d_obstacles, int nObs, float* state, float* ctrl,
+                       int* parent, int* origin, uint8_t* status, long long capacity, sbmp_tree_reanchor* out) override;
+    void replan_from(int root, const float* newRoot, int frontierFrom, const float* goal, const float* d_obstacles,
+                     int nObs, uint64_t seed, sbmp_tree_reanchor* reanchorOut, sbmp_tree_adopt* out) override;
 
     std::vector<sbmp_kernel_stat> kernel_stats() override;
     void path_info(sbmp_path_info* out) override;
@@ -521,6 +549,11 @@ public:
                       long long capacity, sbmp_tree_extract* out) override {
         sync();
         r0().extract_tree(root, useAlive, state, ctrl, parent, origin, newRow, capacity, out);
+    }
+    void reanchor_tree(int root, const float* newRoot, const float* d_obstacles, int nObs, float* state, float* ctrl,
+                       int* parent, int* origin, uint8_t* status, long long capacity, sbmp_tree_reanchor* out) override {
+        sync();
+        r0().reanchor_tree(root, newRoot, d_obstacles, nObs, state, ctrl, parent, origin, status, capacity, out);
     }
 
     std::vector<sbmp_kernel_stat> kernel_stats() override { return r0().kernel_stats(); }

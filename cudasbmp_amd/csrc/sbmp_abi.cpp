@@ -584,6 +584,37 @@ sbmp_status sbmp_kgmt_replan(sbmp_kgmt* h, int root, int useAlive, int frontierF
     });
 }
 
+sbmp_status sbmp_kgmt_reanchor_tree(sbmp_kgmt* h, int root, const float newRoot[4], const float* d_obstacles,
+                                    int obstaclesCount, float* state, float* ctrl, int* parent, int* origin,
+                                    uint8_t* status, long long capacity, sbmp_tree_reanchor* out) {
+    return guarded([&] {
+        PLANNER(h);
+        P.reanchor_tree(root, newRoot, d_obstacles, obstaclesCount, state, ctrl, parent, origin, status, capacity, out);
+    });
+}
+
+sbmp_status sbmp_kgmt_replan_from(sbmp_kgmt* h, int root, const float newRoot[4], int frontierFrom,
+                                  const float goal[7], const float* d_obstacles, int obstaclesCount, uint64_t seed,
+                                  sbmp_tree_reanchor* reanchorOut, sbmp_tree_adopt* adoptOut) {
+    return guarded([&] {
+        PLANNER(h);
+        if (h->borrowed) throw Error(SBMP_ERR_STATE, "replanning by adoption is not supported on a batch member");
+        P.replan_from(root, newRoot, frontierFrom, goal, d_obstacles, obstaclesCount, seed, reanchorOut, adoptOut);
+    });
+}
+
+sbmp_status sbmp_tree_reanchor_batch(const sbmp_tree_recheck_args* args, const float newRoot[4], float* d_outState,
+                                     uint8_t* d_alive, uint8_t* status, sbmp_tree_reanchor* out, void* stream) {
+    return guarded([&] {
+        sbmp::tree_reanchor_batch(args, newRoot, d_outState, d_alive, status, out, static_cast<hipStream_t>(stream));
+    });
+}
+
+sbmp_status sbmp_tree_reanchor_batch_host(const sbmp_tree_recheck_args* args, const float newRoot[4], float* outState,
+                                          uint8_t* alive, uint8_t* status, sbmp_tree_reanchor* out) {
+    return guarded([&] { sbmp::tree_reanchor_batch_host(args, newRoot, outState, alive, status, out); });
+}
+
 sbmp_status sbmp_tree_adopt_tables(const sbmp_tree_adopt_tables_args* args, int* R1, int* R1Avail, int* R1Valid,
                                    int* R1Invalid, int* R1Cov, uint32_t* R2bits, sbmp_tree_adopt* out, void* stream) {
     return guarded([&] {

@@ -1,6 +1,6 @@
 // tree_pass.h — the host-side plumbing of a pass over a grown tree, stated once for
-// tree_query.hip, tree_recheck.hip, tree_paths.hip, tree_resample.hip and tree_extract.hip
-// (DESIGN.md §5.8–5.10, §5.12, §5.13).  What a new tree pass gets for free:
+// tree_query.hip, tree_recheck.hip, tree_paths.hip, tree_resample.hip, tree_extract.hip and
+// tree_reanchor.hip (DESIGN.md §5.8–5.10, §5.12, §5.13, §5.15).  What a new tree pass gets for free:
 //   resident_grid            the grid of a grid-stride kernel: what the device holds at once,
 //                            no more than the work needs, and the one error when nothing fits
 //   DevBufs                  the device buffers of one call, freed with it
@@ -8,6 +8,8 @@
 //                            when those buffers go
 //   read_back                results to the host: the copies, the wait, the first error
 //   set_euler_params         what car_euler / point_euler (and their traces) read of a plan
+//   attach_list              another obstacle list for those loops: its device copy, NaN scan
+//                            and grid index, by begin()'s rule for the form
 //   expand_variant_from_env  SBMP_EXPAND_VARIANT, as the planner reads it
 // and on the device (kgmt_device.h): stored_controls, a row's controls as the ChildCtl the
 // Euler loops take, and car_step / point_step, one Euler update of the state.
@@ -19,11 +21,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "kgmt_planner.h"
+#include "obstacle_grid.h"
 
 namespace sbmp {
 
@@ -103,6 +107,45 @@ inline void set_euler_params(KgmtDev& d, int numDisc, float agentLength) {
     d.invAgentLength = (std::frexp(agentLength, &e) == 0.5f) ? 1.0f / agentLength : 0.0f;
     d.rcpNumDisc = markstein_rcp((float)numDisc);
     d.rcpAgentLength = markstein_rcp(agentLength);
+}
+
+// The new list's own device copy (in w: freed with the call), NaN scan and grid index, into d:
+// a copy of the plan's parameters and tree pointers whose obstacle fields are replaced.
+// The form follows begin()'s rule: the grid above kMaxLdsObs boxes (or variant 4), the
+// global loop only for variant 5.
+inline void attach_list(DevBufs& w, KgmtDev& d, const float* d_obstacles, int nObs, int variant, hipStream_t s) {
+    d.obstacles = nullptr;
+    d.nObs = nObs;
+    d.obsNaN = 0;
+    d.gridG = 0;
+    d.gridInvW = d.gridInvH = 0.0f;
+    d.gridStart = nullptr;
+    d.gridBoxes = nullptr;
+    if (nObs == 0) return;
+    float4* obs = w.alloc<float4>((size_t)nObs);
+    SBMP_HIP(hipMemcpyAsync(obs, d_obstacles, sizeof(float4) * (size_t)nObs, hipMemcpyDeviceToDevice, s));
+    std::vector<float> h((size_t)4 * nObs);
+    SBMP_HIP(hipMemcpyAsync(h.data(), d_obstacles, sizeof(float) * h.size(), hipMemcpyDeviceToHost, s));
+    SBMP_HIP(hipStreamSynchronize(s));
+    d.obstacles = obs;
+    for (float v : h)   // wave_cull's and grid_free_fast's separation metric need boxes without NaN
+        if (std::isnan(v)) d.obsNaN = 1;
+    if (!((nObs > kMaxLdsObs && variant != 5) || variant == 4)) return;
+    const HostObstacleGrid g =
+        build_obstacle_grid(h.data(), nObs, d.width, d.height, std::min(grid_resolution(nObs), kMaxLdsGridG));
+    // kGridBatch never-met rows past the end: grid_free_fast loads and tests whole batches
+    const size_t nStart = g.start.size(), nBoxes = g.boxes.size() + kGridBatch;
+    std::vector<float4> boxes(nBoxes, make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY));
+    if (!g.boxes.empty()) std::memcpy(boxes.data(), g.boxes.data(), sizeof(float4) * g.boxes.size());
+    int* gridStart = w.alloc<int>(nStart);
+    float4* gridBoxes = w.alloc<float4>(nBoxes);
+    SBMP_HIP(hipMemcpy(gridStart, g.start.data(), sizeof(int) * nStart, hipMemcpyHostToDevice));
+    SBMP_HIP(hipMemcpy(gridBoxes, boxes.data(), sizeof(float4) * nBoxes, hipMemcpyHostToDevice));
+    d.gridG = g.g;
+    d.gridInvW = g.invW;
+    d.gridInvH = g.invH;
+    d.gridStart = gridStart;
+    d.gridBoxes = gridBoxes;
 }
 
 // Obstacle-list form of the Euler loops (diagnostics / A-B): 0 auto, 1 LDS, 2 LDS x4,

@@ -165,45 +165,6 @@ int recheck_grid(Kernel* fn, size_t lds, long long rows, const char* name) {
 
 using RecheckFn = decltype(&k_tree_recheck<0, kObsGlobal>);
 
-// The new list's own device copy (in w: freed with the call), NaN scan and grid index, into d:
-// a copy of the plan's parameters and tree pointers whose obstacle fields are replaced.
-// The form follows begin()'s rule: the grid above kMaxLdsObs boxes (or variant 4), the
-// global loop only for variant 5.
-void attach_list(DevBufs& w, KgmtDev& d, const float* d_obstacles, int nObs, int variant, hipStream_t s) {
-    d.obstacles = nullptr;
-    d.nObs = nObs;
-    d.obsNaN = 0;
-    d.gridG = 0;
-    d.gridInvW = d.gridInvH = 0.0f;
-    d.gridStart = nullptr;
-    d.gridBoxes = nullptr;
-    if (nObs == 0) return;
-    float4* obs = w.alloc<float4>((size_t)nObs);
-    SBMP_HIP(hipMemcpyAsync(obs, d_obstacles, sizeof(float4) * (size_t)nObs, hipMemcpyDeviceToDevice, s));
-    std::vector<float> h((size_t)4 * nObs);
-    SBMP_HIP(hipMemcpyAsync(h.data(), d_obstacles, sizeof(float) * h.size(), hipMemcpyDeviceToHost, s));
-    SBMP_HIP(hipStreamSynchronize(s));
-    d.obstacles = obs;
-    for (float v : h)   // wave_cull's and grid_free_fast's separation metric need boxes without NaN
-        if (std::isnan(v)) d.obsNaN = 1;
-    if (!((nObs > kMaxLdsObs && variant != 5) || variant == 4)) return;
-    const HostObstacleGrid g =
-        build_obstacle_grid(h.data(), nObs, d.width, d.height, std::min(grid_resolution(nObs), kMaxLdsGridG));
-    // kGridBatch never-met rows past the end: grid_free_fast loads and tests whole batches
-    const size_t nStart = g.start.size(), nBoxes = g.boxes.size() + kGridBatch;
-    std::vector<float4> boxes(nBoxes, make_float4(INFINITY, INFINITY, -INFINITY, -INFINITY));
-    if (!g.boxes.empty()) std::memcpy(boxes.data(), g.boxes.data(), sizeof(float4) * g.boxes.size());
-    int* gridStart = w.alloc<int>(nStart);
-    float4* gridBoxes = w.alloc<float4>(nBoxes);
-    SBMP_HIP(hipMemcpy(gridStart, g.start.data(), sizeof(int) * nStart, hipMemcpyHostToDevice));
-    SBMP_HIP(hipMemcpy(gridBoxes, boxes.data(), sizeof(float4) * nBoxes, hipMemcpyHostToDevice));
-    d.gridG = g.g;
-    d.gridInvW = g.invW;
-    d.gridInvH = g.invH;
-    d.gridStart = gridStart;
-    d.gridBoxes = gridBoxes;
-}
-
 // Per-call scratch (in w): the status bytes, two anc and two dead arrays (twoPairs; else only
 // anc[0] and dead[1] are used) and the accumulators.
 struct RecheckScratch {

@@ -363,6 +363,25 @@ class KGMT:
         from .tree_adopt import replan
         return replan(self, goal, d_obstacles, count, seed, root, alive, frontier_from)
 
+    def reanchor(self, state, root: int = 0, obstacles=(), obstaclesCount: Optional[int] = None) -> dict:
+        """The subtree below row `root` re-anchored on the measured state (x, y, theta, v)
+        (sbmp_kgmt_reanchor_tree; include/sbmp/tree_reanchor.h): extract(root) with every row kept,
+        then every row replayed from its parent's new state with its stored controls against
+        `obstacles` ((n, 4) array, or a device pointer with obstaclesCount), one launch per level.
+        Returns, in the extracted numbering, state (rows, 4) with the new states (a dead row keeps
+        its stored one), ctrl, parent, origin, status (SBMP_ROW_*), alive (rows,) uint8 and summary,
+        a dict rows, alive, blocked, orphan, cut, firstDead, levels.  The plan goes on unchanged."""
+        from .tree_reanchor import reanchor
+        return reanchor(self, state, root, obstacles, obstaclesCount)
+
+    def replan_from(self, state, goal, d_obstacles, count: int, seed: int, root: int = 0,
+                    frontier_from: int = 0) -> dict:
+        """reanchor(state, root) against d_obstacles, the rows that stay alive extracted, and the
+        result adopted against `goal` and d_obstacles, all on the device (sbmp_kgmt_replan_from);
+        frontier_from counts in the final numbering.  Returns {"reanchor": summary, "adopt": summary}."""
+        from .tree_reanchor import replan_from
+        return replan_from(self, state, goal, d_obstacles, count, seed, root, frontier_from)
+
     def query_goals(self, goals, radius=None, alive: bool = False) -> dict:
         """Goal discs against the tree as it stands (sbmp_kgmt_query_goals; one k_tree_query pass
         per 16 goals): goals is (Q, 2) with one radius for all, or (Q, 3) rows of (x, y, radius).

@@ -199,6 +199,36 @@ public:
         SBMP_CHECK(sbmp_kgmt_replan(h_, root, useAlive ? 1 : 0, frontierFrom, goal, d_obstacles, obstaclesCount, seed, &s));
         return s;
     }
+    // The subtree below `root` re-anchored on the measured state newRoot = (x, y, theta, v)
+    // (sbmp_kgmt_reanchor_tree; sbmp/tree_reanchor.h): every row replayed from its parent's new
+    // state with its stored controls against d_obstacles.  In extractTree's numbering: state holds
+    // the new states (a dead row keeps its stored one), status one SBMP_ROW_* byte per row.
+    sbmp_tree_reanchor reanchorTree(int root, const float* newRoot, const float* d_obstacles, int obstaclesCount,
+                                    std::vector<float>& state, std::vector<float>& ctrl, std::vector<int>& parent,
+                                    std::vector<int>& origin, std::vector<uint8_t>& status) const {
+        sbmp_tree_extract ex{};   // the size: every row is kept
+        SBMP_CHECK(sbmp_kgmt_extract_tree(h_, root, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &ex));
+        state.assign(4 * (size_t)ex.kept, 0.0f);
+        ctrl.assign(4 * (size_t)ex.kept, 0.0f);
+        parent.assign((size_t)ex.kept, 0);
+        origin.assign((size_t)ex.kept, 0);
+        status.assign((size_t)ex.kept, 0);
+        sbmp_tree_reanchor s{};
+        SBMP_CHECK(sbmp_kgmt_reanchor_tree(h_, root, newRoot, d_obstacles, obstaclesCount, state.data(), ctrl.data(),
+                                           parent.data(), origin.data(), status.data(), ex.kept, &s));
+        return s;
+    }
+    // reanchorTree of the planner's own tree, the rows that stay alive extracted and adopted against
+    // `goal` and d_obstacles, all on the device (sbmp_kgmt_replan_from).  reanchored, if given,
+    // receives the re-anchoring's summary.
+    sbmp_tree_adopt replanFrom(const float* newRoot, const float* goal, const float* d_obstacles, int obstaclesCount,
+                               uint64_t seed, int root = 0, int frontierFrom = 0,
+                               sbmp_tree_reanchor* reanchored = nullptr) {
+        sbmp_tree_adopt s{};
+        SBMP_CHECK(sbmp_kgmt_replan_from(h_, root, newRoot, frontierFrom, goal, d_obstacles, obstaclesCount, seed,
+                                         reanchored, &s));
+        return s;
+    }
     // The two calls on any planner handle (KGMTBatch passes a member's).
     static sbmp_tree_extract extractTreeOf(sbmp_kgmt* h, int root, bool useAlive, std::vector<float>& state,
                                            std::vector<float>& ctrl, std::vector<int>& parent, std::vector<int>& origin,

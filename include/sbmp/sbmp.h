@@ -430,6 +430,45 @@ sbmp_status sbmp_kgmt_adopt_tree(sbmp_kgmt* h, const sbmp_tree_adopt_args* args,
 sbmp_status sbmp_kgmt_replan(sbmp_kgmt* h, int root, int useAlive, int frontierFrom, const float goal[7],
                              const float* d_obstacles, int obstaclesCount, uint64_t seed, sbmp_tree_adopt* out);
 
+/* Re-anchor a tree on a measured state (include/sbmp/tree_reanchor.h states the rule; DESIGN.md
+ * §5.15; no reference counterpart).  The tree's root is row 0.  Every row is replayed from its
+ * parent's NEW state with the row's stored (a, steering, duration), by the expand step's own
+ * Euler loop against the given boxes, level by level from the new root state; each row gets one
+ * status byte and one output state:
+ *   row 0                    SBMP_ROW_FREE, alive, the new root state
+ *   parent not in [0, r)     SBMP_ROW_ORPHAN, dead (nothing is read through it)
+ *   parent dead              SBMP_ROW_FREE | SBMP_ROW_CUT, dead, not replayed
+ *   parent alive             all numDisc steps valid: SBMP_ROW_FREE, alive, the replay's end state;
+ *                            else SBMP_ROW_BLOCKED, dead
+ * A dead row keeps its stored state bit for bit.  Controls, parents and costs do not change. */
+typedef struct sbmp_tree_reanchor {
+    int rows, alive, blocked, orphan, cut;   /* rows = alive + blocked + orphan + cut */
+    int firstDead;                           /* lowest row not alive, -1 if none */
+    int levels;                              /* 1 + the most edges between a row and the top of its chain */
+} sbmp_tree_reanchor;
+/* sbmp_kgmt_extract_tree of `root` with every row kept, into memory of the call's own, re-anchored
+ * on newRoot (x, y, theta, v) with the handle's agent, numDisc, agentLength, workspace and
+ * obstacle-form rule against d_obstacles (device, obstaclesCount boxes).  The answer is in the
+ * extracted numbering.  Host outputs, each may be NULL: state (the new states), ctrl, parent and
+ * origin as sbmp_kgmt_extract_tree gives them and status (one byte a row) hold `capacity` rows.
+ * *out is set in every case, out->rows = the extracted rows: with capacity < out->rows and any of
+ * the five given the call fails with SBMP_ERR_INVALID_ARGUMENT, so a NULL / 0 call returns the
+ * size to allocate.  A non-finite newRoot, root outside [0, R), a bad obstacle list or out NULL:
+ * SBMP_ERR_INVALID_ARGUMENT.  State, waiting and handles as sbmp_kgmt_extract_tree: it only reads
+ * the tree, and the plan goes on unchanged. */
+sbmp_status sbmp_kgmt_reanchor_tree(sbmp_kgmt* h, int root, const float newRoot[4], const float* d_obstacles,
+                                    int obstaclesCount, float* state, float* ctrl, int* parent, int* origin,
+                                    uint8_t* status, long long capacity, sbmp_tree_reanchor* out);
+/* On the device: extract `root` (every row kept), re-anchor on newRoot against d_obstacles,
+ * extract the alive rows, and sbmp_kgmt_adopt_tree of the result with goal, d_obstacles and seed.
+ * frontierFrom counts in the final numbering, as for sbmp_kgmt_replan.  reanchorOut (may be NULL)
+ * gets the re-anchoring's summary, adoptOut the adoption's.  Refusals and out-of-scope handles
+ * are sbmp_kgmt_adopt_tree's, plus a non-finite newRoot; a refusal leaves the previous plan as
+ * it was. */
+sbmp_status sbmp_kgmt_replan_from(sbmp_kgmt* h, int root, const float newRoot[4], int frontierFrom,
+                                  const float goal[7], const float* d_obstacles, int obstaclesCount, uint64_t seed,
+                                  sbmp_tree_reanchor* reanchorOut, sbmp_tree_adopt* adoptOut);
+
 sbmp_status sbmp_kgmt_kernel_stats(sbmp_kgmt* h, sbmp_kernel_stat* out, int capacity, int* count);
 /* The form of the hot path chosen at the last begin() (sbmp_path_info). */
 sbmp_status sbmp_kgmt_path_info(sbmp_kgmt* h, sbmp_path_info* out);
@@ -713,6 +752,23 @@ sbmp_status sbmp_tree_adopt_tables(const sbmp_tree_adopt_tables_args* args, int*
                                    void* stream /* hipStream_t; NULL: default */);
 sbmp_status sbmp_tree_adopt_tables_host(const sbmp_tree_adopt_tables_args* args, int* R1, int* R1Avail, int* R1Valid,
                                         int* R1Invalid, int* R1Cov, uint32_t* R2bits, sbmp_tree_adopt* out);
+/* sbmp_tree_reanchor_batch: the re-anchoring of sbmp_kgmt_reanchor_tree (k_reanchor_*) over caller
+ * rows in the planner's tree layout; args as for sbmp_tree_recheck_batch, all four arrays in
+ * device memory, root = row 0.  newRoot: host, 4 finite floats.  d_outState (rows x 4 floats) and
+ * d_alive (rows bytes, 0 / 1) are device memory, so the result can stay there; each may be NULL.
+ * status (host, rows bytes, may be NULL) and *out as above.  depthBound: an upper bound on the
+ * rows of any parent chain (<= 0: rows, always sufficient), which sets the number of
+ * pointer-jumping passes of the depth count.  A bound that is too small is detected and refused
+ * with SBMP_ERR_INVALID_ARGUMENT before any row is replayed: a level would read a parent's state
+ * before it is written.  Waits for the result.  sbmp_tree_reanchor_batch_host takes the same
+ * arrays in host memory (outState and alive included) and applies the literal rule in one
+ * ascending loop (reanchor_rows_host of include/sbmp/tree_reanchor.h); it needs no device and
+ * does not read depthBound. */
+sbmp_status sbmp_tree_reanchor_batch(const sbmp_tree_recheck_args* args, const float newRoot[4], float* d_outState,
+                                     uint8_t* d_alive, uint8_t* status, sbmp_tree_reanchor* out,
+                                     void* stream /* hipStream_t; NULL: default */);
+sbmp_status sbmp_tree_reanchor_batch_host(const sbmp_tree_recheck_args* args, const float newRoot[4], float* outState,
+                                          uint8_t* alive, uint8_t* status, sbmp_tree_reanchor* out);
 
 /* The threshold the kernel compares d2 with (host-only, no device needed): *t = the largest
  * float d2 with sqrtf(d2) < r, found by bisecting the float bit patterns with that rule;
