@@ -1,9 +1,12 @@
 """Adoption on the GPU (tree_adopt.hip; include/sbmp/tree_adopt.h).
 
   the kernels       sbmp_tree_adopt_tables equals the numpy model and the host twin bit for bit on the
-                    whole table (tests/tree_adopt_cases.py); two calls give identical bytes
-  the planner       adopt() then regions(), tree(), iter_log() before any step; a refused adoption
-                    leaves the previous plan's state_hash() unchanged
+                    whole table (tests/tree_adopt_cases.py); two calls give identical bytes.  Its cases
+                    past one sweep of the grid (524,288 rows at most; fewer resident workgroups only
+                    start the later rounds sooner) reach the later rounds of k_adopt_scan and k_adopt_seed
+  the planner       adopt() then regions(), tree(), iter_log() before any step, also of SWEEP + 77 rows
+                    (the later rounds of k_adopt_seed's copy); a refused adoption leaves the previous
+                    plan's state_hash() unchanged
   law a             adopt(the single row `initial`) + step(k) is begin(initial) + step(k), bit for bit
                     (tree, regions, unexplored, rng; iter_log one iteration later), k = 1, 3, 8, four
                     scenarios, both step forms: through begin()'s side this ties adopted runs to the oracle
@@ -169,6 +172,41 @@ def test_adopt_then_read_before_any_step(which, form, monkeypatch):
     assert log.tolist() == [[1, R, 0, 0, 0, 0, 0, R, -1]], log       # row 1 is the adoption: S = A = 0
     r = g.result()
     assert (r.iterations, r.treeSize, r.goalIndex, r.stalled) == (1, R, -1, 0)    # the adoption is no stall
+
+
+def test_adopt_of_a_tree_past_one_sweep(monkeypatch):
+    """SWEEP + 77 rows into a planner of 2 SWEEP slots: k_adopt_seed's copy into treeState, treeCtrl
+    and treeParent goes round its grid-stride loop a second time (only the planner entry copies).
+    Random rows inside the workspace, random lower parents, distinct costs, the frontier at the
+    last 64 rows, a goal no row holds; tree() and regions() before any step."""
+    from cudasbmp_amd import KGMT
+    set_form(monkeypatch, "k_step")
+    S = ac.SWEEP
+    state, ctrl, parent, f = ac.planner_past_sweep()
+    R = len(parent)
+    assert R == S + 77 and f == R - 64
+    cfg = dict(DEMO, maxTreeSize=2 * S, numIterations=3)
+    far_goal = (-5.0, -5.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+    g = KGMT(**cfg)
+    out = g.adopt(state, parent, ctrl, far_goal, None, 0, 7, frontier_from=f)
+    want, summary = model_regions(state, cfg, (far_goal[0], far_goal[1], cfg["goalThreshold"]), f)
+    assert out == summary and (out["rows"], out["treeSize"], out["gLo"], out["goalRow"]) == (R, R, f, -1)
+    assert (out["nonFinite"], out["outOfGrid"]) == (0, 0)
+    ts, tp, tc = g.tree()
+    assert len(tp) == 2 * S
+    for name, got, src in (("state", ts[:R, :4], state), ("controls", ts[:R, 4:7], ctrl[:, :3]), ("cost", tc[:R], ctrl[:, 3])):
+        bad = np.flatnonzero((u32(got) != u32(src)).reshape(R, -1).any(axis=1))
+        assert len(bad) == 0, f"{name}: {len(bad)} rows differ, first {bad[:8].tolist()} ({(bad >= S).sum()} at or past SWEEP)"
+    bad = np.flatnonzero(tp[:R] != parent)
+    assert len(bad) == 0, f"parent: {len(bad)} rows differ, first {bad[:8].tolist()}"
+    assert not ts[R:].any() and (tp[R:] == -1).all() and not tc[R:].any()
+    got = g.regions()
+    for k in want:
+        assert got[k].dtype == want[k].dtype and np.array_equal(u32(got[k]), u32(want[k])), f"regions {k}"
+    assert want["R1"].sum() == R and want["R2Avail"].all()
+    assert g.iter_log().tolist() == [[1, R, 0, 0, 0, 0, 0, R, -1]]
+    r = g.result()
+    assert (r.iterations, r.treeSize, r.goalIndex, r.stalled) == (1, R, -1, 0)
 
 
 def test_refused_adoption_leaves_the_previous_plan(monkeypatch):

@@ -9,6 +9,11 @@ entries, and two calls byte for byte.  Planner level: KGMT.extract against the m
 after a re-check, re-rooted on the solution path, between steps, on a local shard group and on a
 batch member.
 
+The table's rows-sweep+77, rows-2sweep+1, rows-tiles+1 and root-past-sweep cases take every
+grid-stride loop of the six kernels past its first round (one sweep is at most 524,288 rows, 2,048
+tiles; fewer resident workgroups only start the later rounds sooner) and k_extract_offsets to nine
+rounds; tests/test_tree_pass_seams_oracle.py shows on the CPU which broken loops they catch.
+
 Trees of 2^28 rows and more, where 16 x row passes 2^32, are not run here: they do not fit in a few
 seconds.
 """

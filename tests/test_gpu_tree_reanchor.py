@@ -3,7 +3,10 @@
 Step level: sbmp_tree_reanchor_batch on every case of tests/tree_reanchor_cases.py against the
 model (tests/tree_reanchor_model.py: the CPU oracle's replay level by level + numpy) and against
 the host twin, bit for bit; every obstacle form; two calls give the same bytes; a depth bound
-below the longest chain is refused.  Three laws tie the new kernels to the ones that exist:
+below the longest chain is refused.  The table's cases of SWEEP + 77 rows (one sweep of the grid is
+at most 524,288 rows; fewer resident workgroups only start the later rounds sooner) take init, jump,
+hist, scatter and one level past their first round, and its rows-2047 .. 2049 and chain-2046 .. 2048
+cases stand either side of the 2,048 depth counters k_reanchor_hist keeps in LDS.  Three laws tie the new kernels to the ones that exist:
   a  s0 = the stored root and the planner's own boxes: every row recheck calls alive is alive
      here and keeps its stored state bit for bit (invariant I1)
   b  re-anchor on a displaced s0, extract the alive rows, re-check the result against the same
@@ -111,8 +114,9 @@ def test_forced_forms_on_a_deep_tree(variant, monkeypatch):
 
 
 @pytest.mark.parametrize("build", [lambda: rc.grown(*tc.MAIN, "moved"), lambda: rc.chain(257, "last", "same"),
-                                   rc.far_parent, lambda: rc.boxes_case(3000), lambda: rc.star(rc.STAR_ROWS)],
-                         ids=["grown", "chain", "far-parent", "grid", "star"])
+                                   rc.far_parent, lambda: rc.boxes_case(3000), lambda: rc.star(rc.STAR_ROWS),
+                                   rc.big_star, lambda: rc.recursive(0)],
+                         ids=["grown", "chain", "far-parent", "grid", "star", "star-sweep+77", "recursive-sweep+77"])
 def test_two_calls_give_identical_bytes(build):
     """The order of the rows inside a level is whatever the atomics give: no output byte depends on it."""
     c = build()

@@ -3,8 +3,9 @@ include/sbmp/tree_resample.h).
 
 Step level: sbmp_tree_resample_batch against the model (tests/tree_resample_model.py) and against
 the host twin, bit for bit: grown trees, sample totals and request counts round the wave and the
-workgroup sizes, the crafted chains, both v / L forms and the IEEE fallback, mixed statuses, and
-one path whose state array passes 2^32 bytes.  Planner level: KGMT.resample against the model over
+workgroup sizes, the crafted chains, both v / L forms and the IEEE fallback, mixed statuses, 715
+requests whose samples pass one sweep of k_path_resample's grid (524,288 samples at most), and one
+path whose state array passes 2^32 bytes.  Planner level: KGMT.resample against the model over
 tree(), between steps, on a local shard group and on a batch member.
 
 A total of 1 sample cannot occur: a path has at least two samples (the rule's n = floor(T / period)
@@ -182,6 +183,44 @@ def test_two_calls_give_identical_bytes():
     nodes = np.arange(-1, len(case.parent), 53, dtype=np.int32)
     a, b = resample(case, nodes, 0.013), resample(case, nodes, 0.013)
     assert all(a[k].tobytes() == b[k].tobytes() for k in a) and len(a["times"]) > 10000
+
+
+def test_many_requests_whose_samples_pass_one_grid_sweep():
+    """About 700 requests, -1 and broken ones among them, 576,712 samples: k_path_resample's lanes
+    of the second sweep bisect the sample offsets for the last twenty requests.  The picked form is
+    taken (the full model takes 0.9 s on the CPU, several times any other test of this file): the
+    model gives every request's first and last 64 samples, and every sample of the requests that
+    hold the offsets SWEEP - 64 .. SWEEP + 64 and total - 64 .. total.  Every sample is compared
+    with the host twin, which tests/test_tree_resample.py holds to the full model on this case."""
+    case, nodes, period = rc.many_requests()
+    kw = rc.params_of(case)
+    ends = lambda n: sorted(set(range(min(64, n))) | set(range(max(0, n - 64), n)))
+    want = resample_model(case.state, case.ctrl, case.parent, nodes, period, pick=ends, **kw)
+    got = resample(case, nodes, period)
+    assert_same_resample(got, resample(case, nodes, period, device=False), label="device vs host")
+    off, total = want["offsets"], int(want["offsets"][-1])
+    assert rc.SWEEP + 1000 <= total <= 1.2 * rc.SWEEP and len(got["times"]) == total
+
+    def part(requests, samples):
+        idx = np.concatenate(samples).astype(np.int64)
+        n = got["counts"][requests]
+        return {"counts": n, "status": got["status"][requests], "offsets": np.concatenate([[0], np.cumsum(n, dtype=np.int64)]),
+                "states": got["states"][idx], "edges": got["edges"][idx], "times": got["times"][idx]}
+
+    every = np.arange(len(nodes))
+    picked = part(every, [off[i] + np.array(ends(int(want["counts"][i])), np.int64) for i in every])
+    assert_same_resample(dict(picked, offsets=got["offsets"]), want, label="device vs model, the ends of every request")
+    holds = lambda a, b: np.flatnonzero((off[:-1] <= b) & (off[1:] > a) & (want["counts"] > 0))
+    whole = np.union1d(holds(rc.SWEEP - 64, rc.SWEEP + 64), holds(total - 64, total - 1))
+    assert 2 <= len(whole) <= 4 and off[whole[0]] < rc.SWEEP - 64 and off[whole[-1] + 1] == total
+    full = resample_model(case.state, case.ctrl, case.parent, nodes[whole], period, **kw)
+    assert_same_resample(part(whole, [np.arange(off[i], off[i + 1]) for i in whole]), full, label="device vs model, whole requests")
+    assert 650 <= len(nodes) <= 750 and len(np.unique(nodes[nodes >= 0])) == (nodes >= 0).sum()
+    status = want["status"]
+    assert (status == NONE).sum() >= 10 and (status == BROKEN).sum() >= 10 and (status == OK).sum() >= 600
+    past = np.flatnonzero((want["offsets"][1:] > rc.SWEEP) & (want["counts"] > 0))      # requests with a sample past the sweep
+    assert len(past) >= 10 and past[0] > 600 and (status[past[0]:] != OK).any()
+    assert (want["counts"][past] >= 2).all() and want["offsets"][past[0]] < rc.SWEEP       # one request straddles it
 
 
 class _DevArray:

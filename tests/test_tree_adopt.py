@@ -65,6 +65,34 @@ def test_the_twin_reaches_every_seam_of_the_table():
     assert any(c.width != c.height for c in cs.values())
 
 
+def test_the_table_passes_one_sweep():
+    """The cases past a sweep are what they are named for, by the model and by the twin."""
+    S = ac.SWEEP
+    assert S == 256 * 8 * 256
+    for name, R in ac.PAST_SWEEP:
+        c = ac.case(name + "-disc")
+        inside = np.flatnonzero(model.in_goal(c.state[:, 0], c.state[:, 1], c.goal))
+        assert c.rows == R > S and inside[0] < S and all(((inside >= k * S) & (inside < (k + 1) * S)).sum() > 1000
+                                                         for k in range(R // S))
+        assert inside[-1] == R - 1 >= R // S * S                  # and the last, partial sweep holds one
+        assert c.model["summary"]["goalRow"] == host(c)["summary"]["goalRow"] == inside[0]
+        assert (c.model["R1"] > 1000).all() and c.model["R1Cov"].min() == 64
+    c = ac.case("goal-past-sweep-disc")
+    assert c.rows == S + 77 and c.model["summary"]["goalRow"] == host(c)["summary"]["goalRow"] == S + 40
+    c = ac.case("goal-both-sweeps-disc")
+    inside = np.flatnonzero(model.in_goal(c.state[:, 0], c.state[:, 1], c.goal))
+    assert inside.tolist() == list(ac.GOAL_BOTH) + [r + S for r in ac.GOAL_BOTH]
+    assert len({r // 64 for r in ac.GOAL_BOTH}) == 3 and len({r // 256 for r in ac.GOAL_BOTH}) == 2
+    assert c.model["summary"]["goalRow"] == host(c)["summary"]["goalRow"] == min(ac.GOAL_BOTH)
+    c = ac.case("counters-past-sweep-nogoal")
+    s = host(c)["summary"]
+    bad = ~np.isfinite(c.state).all(axis=1)
+    assert np.flatnonzero(bad).tolist() == [S + r for r in ac.COUNTERS_NONFINITE] and c.frontier_from == S + 10
+    assert (s["nonFinite"], s["frontierNonFinite"], s["outOfGrid"]) == (7, 4, 9) and s == c.model["summary"]
+    first = model.tables(c.state[:S], c.width, c.N, c.n)["summary"]           # the first sweep counts nothing
+    assert (first["nonFinite"], first["outOfGrid"]) == (0, 0)
+
+
 @pytest.mark.parametrize("x, y", [(5.0, 5.0), (0.0, 0.0), (19.999, 0.1), (1.25, 2.5), (20.0, 3.0), (-0.5, 3.0),
                                   (3.0, float("nan")), (float("inf"), 1.0), (17.3, 17.3)])
 @pytest.mark.parametrize("grid", [dict(width=20.0, N=16, n=8), dict(width=17.3, N=16, n=3), dict(width=20.0, N=1, n=1)])

@@ -77,6 +77,35 @@ def test_the_table_reaches_every_class_and_seam():
     assert xc.case("rows-round+1").rows == rnd + 1 and xc.case("rows-round+1").model["summary"]["kept"] == rnd + 1
 
 
+def test_the_table_passes_one_sweep_of_rows_and_of_tiles():
+    """The cases past a sweep are what they are named for: members on both sides of row SWEEP, three,
+    five and nine rounds of the offsets workgroup, one row in tile SWEEP_TILES, a packed case whose
+    first tile round counts 1 per tile at most outside its last tile, a root past the sweep."""
+    from cudasbmp_amd import tree_extract_info
+    tile, rnd = xc.layout()
+    assert xc.SWEEP == 256 * 8 * 256 and xc.SWEEP_TILES == 2048
+    for what, tiles, rounds in (("sweep+77", 513, 3), ("2sweep+1", 1025, 5), ("tiles+1", 2049, 9)):
+        rows = xc.past_sweep_rows(what)
+        i = tree_extract_info(rows)
+        assert (i["tiles"], i["rounds"]) == (tiles, rounds) and rows > xc.SWEEP
+        for suffix in ("", "-masked"):
+            c = xc.case(f"rows-{what}{suffix}")
+            m, s = c.model["member"], c.model["summary"]
+            assert c.rows == rows and m[:xc.SWEEP].sum() > 1000 and m[xc.SWEEP:].sum() >= 10
+            assert (s["kept"] == rows) == (suffix == "") and (suffix == "" or (s["masked"] > 1000 and s["detached"] > 1000))
+    assert xc.past_sweep_rows("tiles+1") == xc.SWEEP_TILES * tile + 1
+    assert xc.case("rows-tiles+1").model["member"][-1]         # the one row of tile SWEEP_TILES (under the mask: counted, no member)
+    p = xc.case("rows-tiles+1-packed-by-mask")
+    first = xc.SWEEP_TILES * tile - 300
+    per_tile = np.add.reduceat(p.model["member"].astype(np.int64), np.arange(0, p.rows, tile))
+    assert per_tile[0] == 1 and not per_tile[1:-2].any() and per_tile[-2] == 300 and per_tile[-1] == 1
+    assert p.model["summary"]["kept"] == 302 and p.parent[first] == 0 and p.model["origin"][1] == first
+    for suffix in ("", "-masked"):
+        r = xc.case(f"root-past-sweep{suffix}")
+        s = r.model["summary"]
+        assert r.root == xc.SWEEP + 5 == s["below"] and r.rows == 2 * xc.SWEEP + 1 and s["kept"] >= 1
+
+
 # ---------------------------------------------------------------- laws
 LAW_CASES = ("mask-null", "mask-alternating", "mask-bytes-2-0x80", "mask-no-busiest", "root-busiest",
              "root-busiest-alternating", "grown-point-L1-D10", "grown-car-L1.3-D13", "parent-minus1", "star", "chain-257")

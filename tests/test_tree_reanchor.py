@@ -91,6 +91,37 @@ def test_the_table_reaches_what_it_names():
     assert rc.nan_case(5).model[3]["alive"] == 1
 
 
+def test_the_table_passes_one_sweep_and_the_lds_seam():
+    """By the model alone: what the cases past a sweep and round the 2,048 LDS depth counters reach."""
+    S = rc.SWEEP
+    assert S == 256 * 8 * 256 and rc.LDS_DEPTHS == 2048
+    s = rc.big_star().model[3]
+    assert (s["rows"], s["levels"], s["cut"]) == (S + 77, 2, 0) and s["blocked"] > 1000        # level 1: S + 76 rows
+    rec = rc.recursive(0)
+    _, alive, status, s = rec.model
+    # all of 500,165 alive, 5,668 blocked, 18,532 cut occur; this tree has no orphan (every parent is a lower row)
+    assert (s["alive"], s["blocked"], s["cut"], s["orphan"], s["levels"]) == (500165, 5668, 18532, 0, 33)
+    assert alive[S:].any() and (status[S:] != 0).any()
+    d = depths(rec.parent)
+    assert np.bincount(d).max() < S and d[S:].max() > 4 and (np.diff(d) < 0).any()
+    assert rc.hist_depths(S + 77) == S + 77 > rc.LDS_DEPTHS and rc.hist_depths(S + 77, 64) == 65 > s["levels"]
+    assert rc.recursive(64).parent is rec.parent and rc.recursive(64).bound == 64
+    for bound in (4, 9):
+        c = rc.short_bound_past_sweep(bound)
+        d = depths(c.parent)
+        assert c.model[3]["levels"] == 10 and np.flatnonzero(d > 4).min() == S + 72 and c.refused == (bound == 4)
+        assert c.bound == bound and (1 << 2) < d.max() == 9 <= (1 << 4)
+    assert [rc.hist_depths(n) for n in rc.SEAM_ROWS] == [2047, 2048, 2049] and rc.hist_depths(2049, 2048) == 2049
+    for e in rc.LONG_CHAIN_EDGES:
+        c = rc.long_chain(e)
+        s = c.model[3]
+        assert (s["rows"], s["alive"], s["levels"]) == (e + 1, e + 1, e + 1)
+        assert depths(c.parent)[-1] == rc.hist_depths(e + 1) - 1 == e       # a row on the last counter
+    assert rc.hist_depths(2047) <= rc.LDS_DEPTHS == rc.hist_depths(2048) < rc.hist_depths(2049)
+    assert rc.hist_depths(2048, 1025) == 2048 and (1 << 11) >= 2047 > (1 << 10) and rc.hist_depths(2048, 1024) == 1025
+    assert not rc.long_chain(2047, 1025).refused and rc.long_chain(2047, 1024, True).refused
+
+
 def test_twin_standalone_under_sanitizers(tmp_path):
     """The twin over exact-size heap arrays, chains, stars, random and crafted parents, as its own
     program under AddressSanitizer and UBSan."""

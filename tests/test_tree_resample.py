@@ -54,6 +54,16 @@ def check(case, nodes, period, depthBound=0, **kw):
     return got, want
 
 
+def test_many_requests_whose_samples_pass_one_grid_sweep():
+    """The case tests/test_gpu_tree_resample.py holds k_path_resample's later sweeps to: the twin
+    equals the model on it, and the total lies where the case says."""
+    case, nodes, period = rc.many_requests()
+    _, want = check(case, nodes, period)
+    total = int(want["offsets"][-1])
+    assert rc.SWEEP + 1000 <= total <= 1.2 * rc.SWEEP
+    assert {NONE, BROKEN, OK} <= set(want["status"].tolist()) and 650 <= len(nodes) <= 750
+
+
 # ---------------------------------------------------------------- grown trees
 @pytest.mark.parametrize("period", rc.PERIODS, ids=rc.PERIOD_IDS)
 @pytest.mark.parametrize("g", tc.GROWN, ids=tc.GROWN_IDS)

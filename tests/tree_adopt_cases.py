@@ -14,6 +14,12 @@ the k_adopt_* kernels.  Every base case appears twice, with a NULL goal disc and
   goal-edge       rows at the disc's radius exactly and one ulp either side; several inside, the lowest wins
   frontier-*      frontierFrom at 0, R - 1 and R
   grid-*          N = 1, n = 1, both, the demo's grid (16, 8), the largest (16, 16), W != H
+  rows-sweep+77, rows-2sweep+1   random rows past one sweep of the grid (SWEEP = 524,288 rows): the later
+                  rounds of k_adopt_scan and k_adopt_seed; the disc holds rows of every sweep
+  goal-past-sweep       the one row inside the disc is row SWEEP + 40
+  goal-both-sweeps      inside rows at r and r + SWEEP, three r in one wave and two in other waves: the lowest wins
+  counters-past-sweep   non-finite and out-of-grid rows at or past row SWEEP only, on both sides of
+                  a frontier that starts at SWEEP + 10
 
 Plain numpy; no GPU and no library at import.
 """
@@ -26,10 +32,15 @@ from typing import Optional
 import numpy as np
 
 import tree_adopt_model as model
+from tree_query_cases import SWEEP
 
 F32 = np.float32
 ROW_COUNTS = (1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025)
 ONE_CELL_ROWS = 65537
+PAST_SWEEP = (("rows-sweep+77", SWEEP + 77), ("rows-2sweep+1", 2 * SWEEP + 1))
+GOAL_BOTH = (643, 650, 700, 760, 1090)         # and the rows one sweep above them
+COUNTERS_NONFINITE = (2, 5, 9, 12, 30, 64, 70)  # rows past SWEEP; the frontier starts at SWEEP + 10
+COUNTERS_OUTSIDE = (3, 7, 50, 63, 76)
 DEMO_GRID = dict(width=20.0, height=20.0, N=16, n=8)      # demos/main.cu
 DEMO_GOAL = (2.0, 18.0, 0.5)
 
@@ -138,6 +149,70 @@ def goal_edge_rows(goal):
     return _rows(xy)
 
 
+def _outside_the_disc(st, goal, but=()) -> np.ndarray:
+    """`st` with every row inside the disc moved to (1.5, 1.5), except the rows `but`."""
+    inside = model.in_goal(st[:, 0], st[:, 1], goal)
+    inside[list(but)] = False
+    st[inside, :2] = (1.5, 1.5)
+    return st
+
+
+def goal_past_sweep():
+    """(state, goal): SWEEP + 77 random rows, of which row SWEEP + 40 alone lies inside the disc."""
+    R, row = SWEEP + 77, SWEEP + 40
+    st = random_rows(R, 41)
+    st[row, :2] = (12.25, 7.5)
+    goal = (12.0, 7.5, 0.5)
+    st = _outside_the_disc(st, goal, but=(row,))
+    assert np.flatnonzero(model.in_goal(st[:, 0], st[:, 1], goal)).tolist() == [row]
+    return st, goal
+
+
+def goal_both_sweeps():
+    """(state, goal): the rows GOAL_BOTH and the rows one sweep above them inside the disc, no other:
+    three of them in one wave (640 .. 703), one in the next wave, one in another workgroup."""
+    R = SWEEP + 1100
+    goal = (12.0, 7.5, 0.5)
+    st = _outside_the_disc(random_rows(R, 43), goal)
+    rows = np.array(GOAL_BOTH + tuple(r + SWEEP for r in GOAL_BOTH))
+    st[rows, 0] = np.linspace(11.8, 12.2, len(rows), dtype=F32)
+    st[rows, 1] = 7.5
+    assert np.array_equal(np.flatnonzero(model.in_goal(st[:, 0], st[:, 1], goal)), np.sort(rows))
+    return st, goal
+
+
+def counters_past_sweep() -> np.ndarray:
+    """SWEEP + 77 rows whose non-finite and out-of-grid rows all lie at or past row SWEEP; the
+    frontier starts at SWEEP + 10, so rows COUNTERS_NONFINITE lie on both sides of it."""
+    st = random_rows(SWEEP + 77, 47)
+    for i, r in enumerate(COUNTERS_NONFINITE):
+        st[SWEEP + r, i % 4] = (np.nan, np.inf, -np.inf, np.nan)[i % 4]
+    for i, r in enumerate(COUNTERS_OUTSIDE):
+        st[SWEEP + r, i % 2] = (-1.0, 25.0, 20.0)[i % 3]
+    return st
+
+
+@functools.lru_cache(maxsize=None)
+def planner_past_sweep():
+    """(state, ctrl, parent, frontier_from) of the planner-level adoption past one sweep: SWEEP + 77
+    random rows inside the workspace, random lower parents, distinct costs, the frontier at the last
+    64 rows.  k_adopt_seed copies them into the planner's tree, which only the planner entry asks for."""
+    R = SWEEP + 77
+    rng = np.random.default_rng(51)
+    state = random_rows(R, 51)
+    ctrl = np.zeros((R, 4), dtype=F32)
+    ctrl[:, 0] = rng.uniform(-5.0, 5.0, R)
+    ctrl[:, 1] = rng.uniform(-3.1, 3.1, R)
+    ctrl[:, 2] = rng.uniform(0.06, 0.3, R)
+    ctrl[:, 3] = rng.permutation(R).astype(F32)             # distinct: R < 2^24
+    parent = (rng.random(R) * np.arange(R)).astype(np.int32)
+    parent[0] = -1
+    assert len(np.unique(ctrl[:, 3])) == R and (parent[1:] < np.arange(1, R)).all() and (parent[1:] >= 0).all()
+    for a in (state, ctrl, parent):
+        a.setflags(write=False)
+    return state, ctrl, parent, R - 64
+
+
 def _base_cases() -> list:
     """(name, state, grid, goal-with-disc, frontier_from)."""
     B = []
@@ -170,6 +245,14 @@ def _base_cases() -> list:
         B.append((name, st, dict(width=30.0, height=12.0, **g), (27.0, 10.0, 1.0), 0))
     B.append(("grid-12x30", random_rows(700, 31, 12.0, 30.0), dict(width=12.0, height=30.0, N=16, n=8),
               (10.0, 27.0, 1.0), 350))
+    for name, R in PAST_SWEEP:                 # the disc round the last row holds rows of every sweep: the lowest wins
+        st = random_rows(R, 100 + R % 1000)
+        B.append((name, st, demo, (float(st[R - 1, 0]), float(st[R - 1, 1]), 1.5), 0))
+    st, goal = goal_past_sweep()
+    B.append(("goal-past-sweep", st, demo, goal, 0))
+    st, goal = goal_both_sweeps()
+    B.append(("goal-both-sweeps", st, demo, goal, 0))
+    B.append(("counters-past-sweep", counters_past_sweep(), demo, (10.0, 10.0, 1.0), SWEEP + 10))
     return B
 
 
@@ -190,6 +273,7 @@ def _ids() -> tuple:
         "one-cell", "r1-lines", "r2-lines", "r2-lines-17.3", "round-up", "outside", "outside-12x30", "nonfinite",
         "goal-edge", "goal-edge-up", "goal-edge-down", "goal-radius-zero", "frontier-0", "frontier-last", "frontier-R",
         "grid-N1-n1", "grid-N1-n16", "grid-N16-n1", "grid-N3-n5", "grid-largest", "grid-demo", "grid-12x30"]
+    names += [name for name, _ in PAST_SWEEP] + ["goal-past-sweep", "goal-both-sweeps", "counters-past-sweep"]
     return tuple(n + s for n in names for s in ("-nogoal", "-disc"))
 
 

@@ -7,13 +7,18 @@ planner's layout, a root and a keep mask (None: the NULL mask); the model's answ
   chain-*     single chains of 1, 2, 3, 64, 65, 257 rows
   star        a star of 257 rows
   rows-*      row counts round the wave and the workgroup; round the tile and one row more than a
-              full round of the offsets workgroup, both read from sbmp_tree_extract_info
-  mask-*      NULL and all ones, all zero, the root only, alternating, bytes 2 and 0x80 as kept, a
+              full round of the offsets workgroup, both read from sbmp_tree_extract_info; past one
+              sweep of the row grid (SWEEP + 77 and 2 SWEEP + 1 rows: the later rounds of mark, jump
+              and gather, three and five rounds of the offsets workgroup) and one row past one sweep
+              of the tile grid (2,048 tiles + 1 row: the second round of count and number), that one
+              also with every member but row 0 in the last 301 rows
+  mask-*    NULL and all ones, all zero, the root only, alternating, bytes 2 and 0x80 as kept, a
               zero in the middle of a chain (its kept descendants are detached), a zero on the
               row with most descendants, every member packed into the last tile, every first
               lane of a wave and every last
   root-*      0, a leaf, R - 1, the row with most descendants, the D6 rows 993-999 of
-              tests/goal_scenarios.py's reference-clear tree, a row that is masked
+              tests/goal_scenarios.py's reference-clear tree, a row that is masked, row SWEEP + 5
+              of 2 SWEEP + 1 (`below` counts more than one sweep of rows)
   parent-*    the crafted parents of the re-check cases (-1, r, r + 1, INT_MIN, INT_MAX) on
               ordinary rows and on the root itself
 
@@ -31,8 +36,11 @@ import numpy as np
 
 import tree_recheck_cases as tc
 from tree_extract_model import extract_model
+from tree_query_cases import SWEEP
 from tree_recheck_model import descendants
 
+SWEEP_TILES = SWEEP // 256        # tiles of one sweep of k_extract_count / k_extract_number: a workgroup a tile
+PAST_SWEEP = ("sweep+77", "2sweep+1", "tiles+1")
 CHAIN_ROWS = (1, 2, 3, 64, 65, 257)
 ROW_COUNTS = (1, 63, 64, 65, 255, 256, 257)
 D6_ROWS = tuple(range(993, 1000))
@@ -67,6 +75,13 @@ def layout():
     from cudasbmp_amd import tree_extract_info
     i = tree_extract_info(0)
     return i["tileRows"], i["tileRows"] * i["roundTiles"]
+
+
+def past_sweep_rows(what) -> int:
+    """Row counts past one sweep of the row grid (SWEEP rows: mark, jump, gather) and one row past
+    one sweep of the tile grid (SWEEP_TILES tiles: count, number)."""
+    tile, _ = layout()
+    return {"sweep+77": SWEEP + 77, "2sweep+1": 2 * SWEEP + 1, "tiles+1": SWEEP_TILES * tile + 1}[what]
 
 
 @functools.lru_cache(maxsize=None)
@@ -153,6 +168,36 @@ def all_cases() -> list:
                 tile, rnd = layout()
                 return seam({"tile-1": tile - 1, "tile": tile, "tile+1": tile + 1, "round+1": rnd + 1}[what], masked)
             add(f"rows-{what}{'-masked' if masked else ''}", build)
+
+    # past one sweep of the row grid and of the tile grid
+    for what in PAST_SWEEP:
+        for masked in (False, True):
+            add(f"rows-{what}{'-masked' if masked else ''}",
+                functools.partial(lambda what, masked: seam(past_sweep_rows(what), masked), what, masked))
+
+    def packed_past_tiles():
+        """Root 0 and, by the mask, the rows from 300 below the end of tile SWEEP_TILES - 1 on: every
+        tile of the first tile round but the last counts 1 or 0, tile SWEEP_TILES counts its one row."""
+        n = past_sweep_rows("tiles+1")
+        first = n - 1 - 300
+        c = synthetic(n, seed=7, packed_from=first)
+        p = c.parent.copy()
+        p[first] = 0
+        return of(ExtractCase(c.name, c.state, c.ctrl, p), "rows-tiles+1-packed-by-mask", 0,
+                  _mask(n, lambda r: (r == 0) | (r >= first)))
+
+    add("rows-tiles+1-packed-by-mask", packed_past_tiles)
+
+    def root_past_sweep(masked):
+        c = seam(past_sweep_rows("2sweep+1"), masked)
+        keep = c.keep
+        if masked:
+            keep = keep.copy()
+            keep[SWEEP + 5] = 1
+        return of(c, f"root-past-sweep{'-masked' if masked else ''}", SWEEP + 5, keep)
+
+    add("root-past-sweep", functools.partial(root_past_sweep, False))
+    add("root-past-sweep-masked", functools.partial(root_past_sweep, True))
 
     # masks over the main tree, root 0
     def masked_main(i):

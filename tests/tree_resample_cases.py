@@ -9,6 +9,7 @@ boxes play no part here.
   bad_durations   a chain whose edges last (the smallest denormal), 0.3, 0, 0.2, -1, NaN, 0.25,
                   +inf, 0.4 seconds
   rounding        one edge and a period whose last grid time rounds to more than the path's time
+  many_requests   about 700 requests whose samples together pass one sweep of k_path_resample's grid
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ import numpy as np
 
 import tree_recheck_cases as tc
 from tree_paths_model import euler_steps
+from tree_query_cases import SWEEP
 
 PERIODS = (0.05, 0.013, float(np.float32(1.05) / np.float32(10)))
 PERIOD_IDS = ("p0.05", "p0.013", "p0.105f")
@@ -95,3 +97,27 @@ def period_for_total(T, total) -> float:
     """A period that gives a path of time T exactly `total` >= 2 samples: floor(T / period) =
     total - 2, aimed at the middle of that interval."""
     return float(T) / (total - 2 + 0.5)
+
+
+MANY_REQUESTS = 700
+
+
+@functools.lru_cache(maxsize=None)
+def many_requests():
+    """(case, nodes, period): about 700 distinct rows of the main grown tree with crafted -1 parents
+    (tests/tree_recheck_cases.py: the busiest row's descendants have broken paths), every 50th
+    request -1, and a period that puts the sample total between SWEEP + 1,000 and 1.2 SWEEP, so
+    the samples of k_path_resample's later sweeps belong to the last requests."""
+    from tree_paths_model import OK, path_of
+    from tree_resample_model import clock_of
+    case = tc.parent_case("minus1")
+    R = len(case.parent)
+    busiest = tc.busiest_row(*tc.MAIN)
+    below = np.flatnonzero(tc.grown(*tc.MAIN).parent == busiest)[:3]
+    nodes = np.unique(np.concatenate([np.arange(1, R, R // MANY_REQUESTS), [busiest, R - 1], below])).astype(np.int32)
+    nodes[::50] = -1
+    par = case.parent.tolist()
+    times = [clock_of(case.ctrl, chain)[-1] for st, chain in (path_of(par, int(n), R) for n in nodes) if st == OK]
+    # sum of floor(T_i / period) + 2 over the ok requests, aimed at 1.1 SWEEP: floor loses half a sample a path
+    period = period_for_total(sum(times), int(1.1 * SWEEP - 1.5 * len(times)))
+    return case, nodes, period
